@@ -7,10 +7,14 @@ kernel launch (muavta_rollout).  Workload = BASELINE config 2b: WPS_hard knobs o
 (`WPS_hard_x2`), 4096 envs per GPU, the 16-agent tile, seeds = global env index.
 
     python bench.py [--gpus N --steps K --warmup W]          # N>1: launched by torch.distributed.run
+    python bench.py --full                                   # + CPU baseline, oracle check and the secondary figures below
+    python bench.py --dump-outputs DIR                       # + the last timed batch's metrics / observation as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 \
         bench.py --gpus 8 --case WPS_burst64 --envs 1024       # BASELINE config 5 (8192 envs, 64x128 tile)
 
-Prints ONE JSON line on rank 0.  `value` is whole-job env-steps/s (all ranks), inputs (seeds) already
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps launches and prints the headline (value, ms_per_step,
+roofline from the timed launches' own HIP events, quality of the last batch); everything that takes runs of its own — cpu_baseline,
+the oracle check, other_tiles and the further N=1 figures — needs --full.  `value` is whole-job env-steps/s (all ranks), inputs (seeds) already
 resident on the device, timed region bracketed by barrier + torch.cuda.synchronize() on both sides,
 max over ranks.  `roofline.achieved` = SURVEY §8(d) algorithmic bytes per env-step x env-steps per
 launch / mean k_rollout duration, the latter measured with HIP events on the library's own stream; the
@@ -345,6 +349,28 @@ def facade_figures(device, case="WPS_hard", seeds=range(8), batch_n=64):
             "facade_last_episode_S_WPS": s_wps}
 
 
+DUMP_BYTES = 60_000_000  # (under 64 MB with the .npy headers, whichever MB is meant)
+
+
+def dump_outputs(out_dir, env, metrics, seeds, write_obs, suffix=""):
+    """--dump-outputs: what a caller of the timed path holds after its last launch, as <out_dir>/<name><suffix>.npy in float32 / float64 — the
+    30 metrics per env (rollout_metrics) and, with the observation write on, the observation dict (observe(): masks as 0 / 1).  Should the batch
+    exceed DUMP_BYTES, a fixed sample of env rows (seeded, the same for the same arguments) is written; `seeds` holds the seeds of the rows kept."""
+    arrays = {"metrics": np.asarray(metrics, dtype=np.float64)}
+    if write_obs:
+        for k, v in env.observe().items():
+            arrays["obs_" + k] = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    arrays["seeds"] = np.asarray(seeds, dtype=np.float64)
+    n = len(arrays["seeds"])
+    row_bytes = sum(a.nbytes for a in arrays.values()) // n
+    if row_bytes * n > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=max(1, DUMP_BYTES // row_bytes), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -354,9 +380,12 @@ def main():
     ap.add_argument("--case", default="WPS_hard_x2")
     ap.add_argument("--interval", type=int, default=None, help="replan interval (default 20; 12 for the escort cases)")
     ap.add_argument("--no-obs", action="store_true", help="skip the per-step observation write (NOT the headline)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the step-API / other-tile / IL figures (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also the CPU baseline + oracle check and the secondary figures (step-API / other-tile / IL / "
+                                                        "policy-loop / facade); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned after its last step (metrics, observation) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="(--full) seconds of CPU-oracle work per process for cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and the oracle check")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the step-API / other-tile / IL figures (profiling runs)")
     ap.add_argument("--abi-collective", action="store_true", help="reduce the metrics through muavta_allreduce_metrics (RCCL behind the C ABI) instead of torch.distributed")
     ap.add_argument("--seed-base", type=int, default=0, help="first global env index (default 0: seeds = global env index)")
     ap.add_argument("--lanes", type=int, default=0, choices=(0, 1, 2), help="state lanes of the handle (muavta_set_lanes): 0 = library default (a second lane is created when a "
@@ -421,10 +450,12 @@ def main():
             dist.destroy_process_group()
         raise SystemExit(f"{n_flagged} env(s) overflowed the {tile} tile (muavta_get ERROR): results would be incomplete")
     summary = reduce_metrics(m, device="cuda" if dist is not None else None, comm=env if args.abi_collective else None)
+    if args.dump_outputs:  # (before the secondary figures, which run other batches on this handle)
+        dump_outputs(args.dump_outputs, env, m, seeds, write_obs, f"_rank{rank}" if world > 1 else "")
 
-    # secondary figures (rank 0 at N=1 only, outside the timed region)
+    # secondary figures (--full, rank 0 at N=1 only, outside the timed region)
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extras = secondary_figures(env, seeds, args, write_obs, barrier)
 
     if rank == 0:
@@ -459,7 +490,7 @@ def main():
                         "n_envs": summary["n_envs"], "capacity_flagged_envs": 0},
         }
         out.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["quality"].update(oracle_check(args.case, args.interval, seeds, m))
             out["cpu_baseline"] = cpu_baseline(args.case, args.interval, args.cpu_seconds)
         print(json.dumps(out))

@@ -6,6 +6,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,3 +44,38 @@ def test_pmc_figures_of_other_kernel_sources_are_not_attached(monkeypatch):
         assert bench.pmc_entry(case, envs) is None and bench.measured_traffic(case, envs) is None
         r = bench.roofline(case, envs, tile, 3.0, None, None, 1, mt, na)
         assert r["traffic"] is None and r["issue"] is None and r["frac"] is not None and "isolated" not in r and "device_frac" not in r
+
+
+class _ObsStandIn:
+    """observe() of a BatchedMultiUAVEnv of the headline tile (dtypes and shapes as muavta_amd.batched returns them), filled from `seed`"""
+
+    def __init__(self, n, seed=0):
+        self.n, self.rng = n, np.random.default_rng(seed)
+
+    def observe(self):
+        n, r = self.n, self.rng
+        return {"tasks": r.random((n, 40, 21), dtype=np.float32), "legal_mask": r.random((n, 16, 40)) < 0.5, "mask": r.random((n, 40)) < 0.5,
+                "agents": r.random((n, 16, 9), dtype=np.float32), "event_flags": r.random((n, 5), dtype=np.float32)}
+
+
+@pytest.mark.parametrize("n", [4096, 32768])
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, n):
+    """--dump-outputs: float32 / float64 .npy files only, the whole batch while it fits the budget, else the same seeded sample of rows in
+    every array and on every run (two dumps of the same batch are identical)."""
+    metrics = np.random.default_rng(1).random((n, 30))
+    seeds = np.arange(n, dtype=np.uint64)
+    dumps = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), _ObsStandIn(n), metrics, seeds, True)
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert set(a) == {"metrics", "seeds", "obs_tasks", "obs_legal_mask", "obs_mask", "obs_agents", "obs_event_flags"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in a) <= 64e6
+    rows = a["seeds"].astype(np.int64)
+    assert len({len(v) for v in a.values()}) == 1 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["metrics"], metrics[rows])
+    assert (len(rows) == n) == (n == 4096)
+    bench.dump_outputs(str(tmp_path / "m"), None, metrics, seeds, False)  # (no observation write: metrics and seeds only)
+    assert sorted(os.listdir(tmp_path / "m")) == ["metrics.npy", "seeds.npy"]

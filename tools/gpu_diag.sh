@@ -7,7 +7,7 @@ OUT=gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" && mkdir -p "$OUT"
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest.log"
 tail -5 "$OUT/pytest.log"
-timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
 cut -c1-600 "$OUT/bench.json"
 rocprofv3 --list-avail > "$OUT/avail.txt" 2>&1
 NAMES=$(grep -o 'SQC_ICACHE_[A-Z_]*\|SQC_INST_[A-Z_]*' "$OUT/avail.txt" | sort -u | tr '\n' ' ')

@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT" && mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest.log"
 tail -3 "$OUT/pytest.log"
-timeout -k 10 400 python bench.py > "$OUT/bench_full.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full > "$OUT/bench_full.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
 cut -c1-200 "$OUT/bench_full.json"
 if [ -f tools/_build/libmuavta_prof.so ]; then
   for c in "WPS_hard_x2 4096" "WPS_escort24 4096" "WPS_burst64 1024"; do

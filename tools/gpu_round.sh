@@ -10,7 +10,7 @@ if [[ " $* " != *" notest "* ]]; then
   timeout -k 10 600 python -m pytest tests -m gpu -x -q > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest.log"
   tail -5 "$OUT/pytest.log"
 fi
-timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 try:

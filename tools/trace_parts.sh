@@ -3,7 +3,7 @@
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/r03trace; mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT/bench -- python3 bench.py --no-cpu-baseline --steps 4 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT/bench -- python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 GPU_MAX_HW_QUEUES=8 PROBE_TORCH=1 rocprofv3 --kernel-trace --output-format csv -d $OUT/probe -- python3 tools/parts_probe.py > $OUT/probe.txt 2> $OUT/probe.err
 python3 - <<'PY'
 import csv, glob, collections
