@@ -224,7 +224,21 @@ int muavta_step_staged(MuavtaEnv* env); /* step with the actions muavta_allocate
 /*   MUAVTA_ALLOC_HUNGARIAN_GATED = the trainers' expert / teacher: HungarianAllocator.allocate_tasks(force=True) under
  *   _should_replan(env, events, replan_interval) with tags Reset_Allocation, New_Threat, Agent_Fail
  *   (experiments/train_pair_cost.py:33-43,109-118); use_visibility=0 gives the Global-Hungarian expert. */
-enum { MUAVTA_ALLOC_HUNGARIAN = 0, MUAVTA_ALLOC_URGENCY_PAIR = 1, MUAVTA_ALLOC_URGENCY_COALITION = 2, MUAVTA_ALLOC_HUNGARIAN_GATED = 3 };
+/*   MUAVTA_ALLOC_CAP_GREEDY = Local-Cap-Greedy: CapabilityGreedy().allocate_tasks(get_live_agents(), _open_tasks(env)) at EVERY step —
+ *   over live agents x tasks with allocatedReqs[ty] < currentReqs[ty], cap > 1e-6 and missing > 0, the first strict maximum of
+ *   min(cap, missing) * 10.0 - |agent.position - task.position| / 1000.0 in agent-major order — then the harness keeps that one pair
+ *   only if its task is in env.last_tasks_info and (with visibility) known to the agent; no other pair is tried
+ *   (TaskAllocation/BehaviourBased/CapabilityGreedy.py:14-47; experiments/wps_eval.py:160-167).  `replan_interval` is ignored and
+ *   n_replans stays 0.
+ *   MUAVTA_ALLOC_PI = Local-PI: PerformanceImpact(replan_interval).allocate_tasks(get_live_agents(), _open_tasks(env), time_step, events,
+ *   agent_known_ids=agent_visibility_map(), max_tasks_per_agent=1) + _apply_assign (TaskAllocation/MarketBased/PerformanceImpact.py:
+ *   49-223; residual slots and eligibility of CBBA.py:10-65; experiments/wps_eval.py:147-159, escort_eval.py:162-175).  Its own gate
+ *   should_replan (interval or any drained event) advances last_plan_step / n_replans on every plan it lets through, empty ones
+ *   included.  use_visibility=0 passes agent_known_ids=None.
+ *   Both run in kernel instantiations of their own.  muavta_rollout_record returns MUAVTA_E_ARG in these two modes; the IL / RL
+ *   entry points (muavta_allocate_scored, muavta_rl_step, muavta_rl_run) run their own planners whatever the mode. */
+enum { MUAVTA_ALLOC_HUNGARIAN = 0, MUAVTA_ALLOC_URGENCY_PAIR = 1, MUAVTA_ALLOC_URGENCY_COALITION = 2, MUAVTA_ALLOC_HUNGARIAN_GATED = 3,
+       MUAVTA_ALLOC_CAP_GREEDY = 4, MUAVTA_ALLOC_PI = 5 };
 int muavta_set_allocator(MuavtaEnv* env, int32_t mode);
 
 /* Token builders of the learned/engineered hybrids, batched over all envs straight from the device state

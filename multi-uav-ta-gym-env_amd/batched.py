@@ -115,8 +115,13 @@ class BatchedMultiUAVEnv:
     def set_allocator(self, name: str = "hungarian"):
         """'hungarian' (Local-/Coalition-Hungarian), 'urgency_pair' (UrgencyPair.plan under the WPS harness gate) or
         'urgency_coalition' (UrgencyCoalition.plan under the escort harness gate, with commit locks) or 'hungarian_gated'
-        (the trainers' expert: allocate_tasks(force=True) under _should_replan(env, events, interval), train_pair_cost.py:33-43)."""
-        self._alloc_mode = {"hungarian": 0, "urgency_pair": 1, "urgency_coalition": 2, "hungarian_gated": 3}[name]
+        (the trainers' expert: allocate_tasks(force=True) under _should_replan(env, events, interval), train_pair_cost.py:33-43),
+        or one of the classical baselines: 'cap_greedy' (Local-Cap-Greedy: CapabilityGreedy's one best pair at every step,
+        experiments/wps_eval.py:160-167; replan_interval is ignored) or 'pi' (Local-PI: PerformanceImpact with
+        max_tasks_per_agent=1 under its own should_replan gate, replan_interval = its interval; wps_eval.py:147-159).  In the
+        two baseline modes rollout_record raises MuavtaError."""
+        self._alloc_mode = {"hungarian": 0, "urgency_pair": 1, "urgency_coalition": 2, "hungarian_gated": 3,
+                            "cap_greedy": 4, "pi": 5}[name]
         self._ck(self.L.muavta_set_allocator(self.h, self._alloc_mode))
 
     GATES = {"force": 0, "trainer": 1, "escort": 2, "allocator": 3}

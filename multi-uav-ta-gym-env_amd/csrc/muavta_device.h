@@ -199,6 +199,7 @@ struct Sim {
 #include "sim/world.inc"
 #include "sim/observe.inc"
 #include "sim/allocate.inc"
+#include "sim/baselines.inc"
 #include "sim/tokens.inc"
 #include "sim/lsap.inc"
 #include "sim/metrics.inc"

@@ -287,7 +287,8 @@ __global__ __launch_bounds__(WG, TILE_MIN_WAVES(TL)) void k_step(const DevCtx* _
   copy16(blob, L.S, sizeof(EnvState<TL>));
 }
 
-template <class TL>
+// BL: the classical baselines (MUAVTA_ALLOC_CAP_GREEDY, MUAVTA_ALLOC_PI; sim/baselines.inc) in instantiations of their own
+template <class TL, bool BL = false>
 __global__ __launch_bounds__(WG) void k_allocate(const DevCtx* __restrict__ ctxp, int interval, int use_vis, int mode,
                                                  int32_t* out_agent, int32_t* out_index, int act_cap, int env_base) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -297,7 +298,8 @@ __global__ __launch_bounds__(WG) void k_allocate(const DevCtx* __restrict__ ctxp
   copy16(L.S, blob, sizeof(EnvState<TL>));
   lds_sync();
   Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, tape_of(ctx, env));
-  sim.allocate(interval, use_vis, mode);
+  if constexpr (BL) sim.allocate_baseline(interval, use_vis, mode);
+  else sim.allocate(interval, use_vis, mode);
   lds_sync();
   if (out_agent) {
     const EnvState<TL>& S = *L.S;
@@ -523,7 +525,7 @@ struct RecordPtrs {
 struct RecBlob { uint32_t w[64]; };  // 256 B: a RecordPtrs<TL> by value
 __global__ void k_store_rec(RecBlob b, uint32_t* dst) { dst[threadIdx.x] = b.w[threadIdx.x]; }
 
-template <class TL, bool REC>
+template <class TL, bool REC, bool BL = false>
 __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned char* lds_own, uint32_t lds_base, int env, int phases, int interval, int use_vis, int mode,
                                                 const RecordPtrs<TL>& rec, int slot, int oslot) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -550,7 +552,8 @@ __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned cha
   }
   lds_sync();
   if (!ABL(9) && (phases & PH_ALLOC) && !(L.S->terminated || L.S->truncated)) {
-    sim.allocate(interval, use_vis, mode);
+    if constexpr (BL) sim.allocate_baseline(interval, use_vis, mode);
+    else sim.allocate(interval, use_vis, mode);
     if (REC && rec.K.task_feats) {  // the sample of step `slot`: tokens + labels of the plan just staged, S_WPS before the step
       const typename Sim<TL>::TokPtrs K = global_tok_ptrs<TL>(rec.K);
       cold_sync();
@@ -562,7 +565,7 @@ __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned cha
   PROF_AT(sim, 20);
 }
 
-template <class TL, bool REC>
+template <class TL, bool REC, bool BL = false>
 __global__ __launch_bounds__(WG, TILE_MIN_WAVES(TL)) void k_rollout(const DevCtx* __restrict__ ctxp, const uint64_t* seeds, int n_steps, int interval, int use_vis,
                                                 int mode, int write_obs, double* metrics, const uint32_t* seedbuf, const RecordPtrs<TL>* __restrict__ recp, int epoch, int env_base) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -656,7 +659,7 @@ static_assert(MUAVTA_PACE_HOLD_POLLS > 0 && MUAVTA_PACE_HOLD_POLLS <= (1 << 16),
       if (threadIdx.x < 16) seen = __hip_atomic_load(pace_row + threadIdx.x, __ATOMIC_RELAXED, MUAVTA_PACE_SCOPE);
     }
 #endif
-    if (ph) rollout_phase<TL, REC>(ctxp, lds_own, lds_base, env, ph, interval, use_vis, mode, rec, k < n_steps ? k : n_steps,
+    if (ph) rollout_phase<TL, REC, BL>(ctxp, lds_own, lds_base, env, ph, interval, use_vis, mode, rec, k < n_steps ? k : n_steps,
                                    (REC && rec.O.tasks && k >= 1 && k <= n_steps) ? k - 1 : -1);
 #if MUAVTA_PACE_PRIO
     if (PACED && k >= 1 && k <= n_steps && (k & (MUAVTA_PACE_EVERY - 1)) == 0) {  // consumed a step later: the load's latency stays off the env's dependent chain
@@ -1046,7 +1049,8 @@ int launch_attr(MuavtaEnv* e) {
   if (lds > 48 * 1024) {
     const void* ks[] = {reinterpret_cast<const void*>(&k_reset<TL>), reinterpret_cast<const void*>(&k_step<TL>), reinterpret_cast<const void*>(&k_allocate<TL>),
                         reinterpret_cast<const void*>(&k_rollout<TL, false>), reinterpret_cast<const void*>(&k_rollout<TL, true>), reinterpret_cast<const void*>(&k_metrics<TL>), reinterpret_cast<const void*>(&k_observe<TL>),
-                        reinterpret_cast<const void*>(&k_tokens<TL>), reinterpret_cast<const void*>(&k_call<TL>), reinterpret_cast<const void*>(&k_context<TL>)};
+                        reinterpret_cast<const void*>(&k_tokens<TL>), reinterpret_cast<const void*>(&k_call<TL>), reinterpret_cast<const void*>(&k_context<TL>),
+                        reinterpret_cast<const void*>(&k_allocate<TL, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, true>)};
     for (const void* k : ks) HIPCHK(e, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate_scored<TL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
   }
@@ -1731,8 +1735,12 @@ int muavta_allocate(MuavtaEnv* e, int32_t interval, int32_t use_vis, int32_t* ac
   if (!e->did_reset) { e->err = "allocate before reset"; return MUAVTA_E_STATE; }
   DeviceScope scope_(e->device);
   MAIN_OP(e);
-  DISPATCH(e, hipLaunchKernelGGL(k_allocate<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, interval, use_vis, e->alloc_mode,
-                                 e->d_act_agent, e->d_act_index, e->A, 0));
+  if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY)
+    DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, interval, use_vis,
+                                   e->alloc_mode, e->d_act_agent, e->d_act_index, e->A, 0))
+  else
+    DISPATCH(e, hipLaunchKernelGGL(k_allocate<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, interval, use_vis, e->alloc_mode,
+                                   e->d_act_agent, e->d_act_index, e->A, 0));
   HIPCHK(e, hipGetLastError());
   e->host_valid = false;
   if (act_agent && act_index) {
@@ -1933,6 +1941,9 @@ static void launch_rollout(MuavtaEnv* e, const uint64_t* ds, int n_steps, int in
     hipLaunchKernelGGL(k_store_rec, dim3(1), dim3(64), 0, stream, blob, (uint32_t*)((char*)e->d_rec + MuavtaEnv::REC_SLOT));
     hipLaunchKernelGGL((k_rollout<TL, true>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
                        n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)((char*)e->d_rec + MuavtaEnv::REC_SLOT), epoch, env_base);
+  } else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) {
+    hipLaunchKernelGGL((k_rollout<TL, false, true>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
+                       n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)e->d_rec, epoch, env_base);
   } else {
     hipLaunchKernelGGL((k_rollout<TL, false>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
                        n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)e->d_rec, epoch, env_base);
@@ -1986,6 +1997,10 @@ int muavta_rollout_record(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, 
   if (!bad && rec->kind < 0 && !any_obs) bad = true;  // nothing to record
   if (bad) {
     if (e) e->err = "muavta_rollout_record: bad argument";
+    return MUAVTA_E_ARG;
+  }
+  if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) {  // the recording kernels carry the Hungarian-family planners only
+    e->err = "muavta_rollout_record: not available with the Cap-Greedy / PI allocators (set_allocator back to a Hungarian mode)";
     return MUAVTA_E_ARG;
   }
   if (any_obs && n_steps > 0) {
@@ -2072,8 +2087,12 @@ int muavta_allocate_part(MuavtaEnv* e, int32_t part, int32_t interval, int32_t u
   int first, count;
   part_range(e, part, &first, &count);
   hipStream_t st = e->part_stream[part];
-  DISPATCH(e, hipLaunchKernelGGL(k_allocate<TL>, dim3(count), dim3(WG), Lds<TL>::bytes(), st, (const DevCtx*)e->d_ctx, interval, use_vis, e->alloc_mode,
-                                 e->d_part_agent, e->d_part_index, e->A, first));
+  if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY)
+    DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, true>), dim3(count), dim3(WG), Lds<TL>::bytes(), st, (const DevCtx*)e->d_ctx, interval, use_vis,
+                                   e->alloc_mode, e->d_part_agent, e->d_part_index, e->A, first))
+  else
+    DISPATCH(e, hipLaunchKernelGGL(k_allocate<TL>, dim3(count), dim3(WG), Lds<TL>::bytes(), st, (const DevCtx*)e->d_ctx, interval, use_vis, e->alloc_mode,
+                                   e->d_part_agent, e->d_part_index, e->A, first));
   HIPCHK(e, hipGetLastError());
   e->host_valid = false;
   if (act_agent && act_index) {
@@ -2129,7 +2148,7 @@ int muavta_prof_read(unsigned long long* out, int reset) {  // diagnostic build 
 #endif
 
 int muavta_set_allocator(MuavtaEnv* e, int32_t mode) {
-  if (!e || (mode < MUAVTA_ALLOC_HUNGARIAN || mode > MUAVTA_ALLOC_HUNGARIAN_GATED)) { if (e) e->err = "unknown allocator mode"; return MUAVTA_E_ARG; }
+  if (!e || (mode < MUAVTA_ALLOC_HUNGARIAN || mode > MUAVTA_ALLOC_PI)) { if (e) e->err = "unknown allocator mode"; return MUAVTA_E_ARG; }
   e->alloc_mode = mode;
   if (e->hl.twin) e->hl.twin->alloc_mode = mode;
   return MUAVTA_OK;

@@ -19,7 +19,7 @@
   //   float32 edge scores 0.5*urgency + 0.3*scarcity - 0.4*dist, clipped to +-0.35, for the first 16 live agents x
   //   first 32 underfilled tasks, subtracted from the Hungarian cost; replan gate = experiments/wps_eval.py:64-74.
   DEV int16_t* pair_info() { return T > 64 ? X.pair_info_big : X.remaining; }
-  // mode 4 (SC, muavta_allocate_scored): the caller's edge scores / task priorities / reserved agents, indexed in the token layout
+  // scored template path (SC = true, muavta_allocate_scored; a template flag, not an alloc_mode value): the caller's edge scores / task priorities / reserved agents, indexed in the token layout
   //   (sc.kind, sc.MT, sc.MA) — PairCostHybrid.plan, AttentionRAH.plan, AttentionCommit / AttentionEscort._plan_from_scores
   //   (HungarianAllocator.py:79-92,123-124,170-179).  sc_list: T bytes of LDS behind the scratch tile (the task list handed to
   //   allocate_tasks, as positions in last_tasks_info, in the token builder's order).  Compiled into k_allocate_scored only.

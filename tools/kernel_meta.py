@@ -10,10 +10,16 @@ import tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
+# names of the bool template arguments behind the tile (k_rollout<TL, REC, BL>, k_allocate<TL, BL>; BL = the baseline allocators)
+FLAGS = {"k_rollout": ("REC", "BL"), "k_allocate": ("BL",)}
+
+
 def short(name):
-    m = re.search(r"(k_\w+?)I4TileILi(\d+)ELi(\d+).*?EE(Lb(\d))?", name)
+    m = re.search(r"(k_\w+?)I4TileILi(\d+)ELi(\d+)E(?:L[ib]\d+E)*E((?:Lb\dE)*)", name)
     if m:
-        return f"{m.group(1)}<{m.group(2)}x{m.group(3)}{',REC' if m.group(5) == '1' else ''}>"
+        bits = re.findall(r"Lb(\d)E", m.group(4))
+        tags = "".join(f",{t}" for t, b in zip(FLAGS.get(m.group(1), ("REC",)), bits) if b == "1")
+        return f"{m.group(1)}<{m.group(2)}x{m.group(3)}{tags}>"
     m = re.search(r"N_1\d+(k_\w+?)E", name)
     return m.group(1) if m else name[:60]
 
