@@ -441,7 +441,9 @@ int muavta_rollout(MuavtaEnv* env, const uint64_t* seeds, int32_t n_steps, int32
  * exactly as if that rollout had overwritten the previous batch — which is what it does on one lane.  What the second lane adds is reach-back:
  *   muavta_rollout_metrics_back(h, 1, out) / muavta_error_flags_back(h, 1, flags)   the batch BEFORE the latest one (its lane is idle or finishing)
  * (MUAVTA_E_STATE when that batch ran on the SAME lane and has been overwritten: in mode 0 a rollout that finds its predecessor finished does
- * not flip — use mode 2 for a pipeline that relies on reach-back), so `rollout(seeds[i + 1]); read batch i` keeps two batches in flight.  muavta_sync waits for both lanes; muavta_device_ptrs returns the current
+ * not flip — use mode 2 for a pipeline that relies on reach-back), so `rollout(seeds[i + 1]); read batch i` keeps two batches in flight.  Settings
+ * (allocator, sub-batches, release log, slot cap) and every muavta_wait_stream made before the second lane exists carry over to it when it is
+ * created, and later ones reach both lanes; a flipped muavta_rollout_record pre-fills obs_done on the lane that runs it.  muavta_sync waits for both lanes; muavta_device_ptrs returns the current
  * lane's buffers (they change with every flip: fetch them again after a seeded rollout, or pin the handle to one lane).  Device memory per
  * handle: lanes x n_envs x (MuavtaDims.state_bytes + 19,968 B of RNG tapes + the observation tensors + 240 B of metrics) + 8 MB. */
 int muavta_set_lanes(MuavtaEnv* env, int32_t lanes);
@@ -607,7 +609,8 @@ int muavta_sync(MuavtaEnv* env);
  * For callers that hand the library device buffers another stream may still be using — e.g. ring tensors a caching allocator
  * recycled while earlier kernels that read them are queued on the framework's stream (torch.cuda.current_stream().cuda_stream)
  * — before muavta_rollout_record / muavta_tokens_device overwrite them.  The wait also covers the sub-batch streams (their next
- * launch is ordered after the handle's stream).  The other direction is muavta_sync (or, without sub-batches, an event on the
+ * launch is ordered after the handle's stream) and both state lanes (muavta_set_lanes): a second lane that does not exist yet waits
+ * on it when it is created — e.g. by the seeded rollout right after this call.  The other direction is muavta_sync (or, without sub-batches, an event on the
  * stream muavta_device_ptrs returns).  The reference has no counterpart: it is single-threaded host code. */
 int muavta_wait_stream(MuavtaEnv* env, void* other_stream);
 /* Metrics written by the last muavta_rollout itself (f64 [N, 30]); no extra launch. */

@@ -1031,6 +1031,7 @@ struct MuavtaEnv {
     unsigned char ring_lane[RING] = {};         // rollout launch k (mod RING) of the HANDLE ran on this lane ...
     unsigned long long ring_no[RING] = {};      // ... as that lane's launch number
     unsigned long long n_launches = 0;
+    std::vector<hipEvent_t> pending_waits;  // muavta_wait_stream events recorded while there was no second lane: one created later waits on them
   } hl;
 };
 static int join_parts(MuavtaEnv* e);  // (sub-batches: defined with the other part helpers in front of the C ABI)
@@ -1436,6 +1437,11 @@ static int ensure_twin(MuavtaEnv* e) {  // create the second lane (same configur
   if (rc != MUAVTA_OK) { if (t) muavta_destroy(t); e->hl.twin_failed = true; return rc; }
   t->alloc_mode = e->alloc_mode;
   if (e->P.slot_cap && muavta_set_slot_cap(t, e->P.slot_cap) != MUAVTA_OK) { muavta_destroy(t); e->hl.twin_failed = true; return MUAVTA_E_HIP; }
+  // the waits the caller queued before this lane existed hold for it too (its part streams fork from its main stream at their first launch)
+  for (hipEvent_t ev : e->hl.pending_waits)
+    if (hipStreamWaitEvent(t->stream, ev, 0) != hipSuccess) { muavta_destroy(t); e->hl.twin_failed = true; return MUAVTA_E_HIP; }
+  for (hipEvent_t ev : e->hl.pending_waits) hipEventDestroy(ev);
+  e->hl.pending_waits.clear();
   t->lane_id = e->lane_id ^ 1;
   t->hl.lanes_mode = 1;  // (a twin never grows a twin)
   e->hl.twin = t;
@@ -1594,6 +1600,8 @@ int muavta_destroy(MuavtaEnv* e) {
   muavta_comm_destroy(e);
   if (e->hl.twin) { muavta_destroy(e->hl.twin); e->hl.twin = nullptr; }
   DeviceScope scope_(e->device);
+  for (hipEvent_t ev : e->hl.pending_waits) hipEventDestroy(ev);
+  e->hl.pending_waits.clear();
   if (e->seed_stream) hipStreamSynchronize(e->seed_stream);
   for (int p = 0; p < MuavtaEnv::MAX_PARTS; p++) {
     if (e->part_stream[p]) { hipStreamSynchronize(e->part_stream[p]); hipStreamDestroy(e->part_stream[p]); }
@@ -1966,6 +1974,9 @@ static int rollout_impl(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, in
   int slot = -1;
   if (seeds) { int rc = enqueue_seeding(e, seeds, &ds, &sb, &slot); if (rc) return rc; }
   e->last_seeded = ds != nullptr;
+  // muavta_rollout_record's obs_done pre-fill: on the stream of the lane that runs the kernel, so only after the lane decision above
+  if (rec && rec->obs_done && n_steps > 0)
+    HIPCHK(e, hipMemsetAsync(rec->obs_done, MUAVTA_OBS_UNWRITTEN, (size_t)n_steps * (size_t)e->n_envs, e->stream));
   const int evi = (int)(e->n_rollouts % MuavtaEnv::EV_RING);
   HIPCHK(e, hipEventRecord(e->ev0[evi], e->stream));
   static const size_t extra_lds = getenv("MUAVTA_EXTRA_LDS") ? (size_t)atoi(getenv("MUAVTA_EXTRA_LDS")) : 0;  // occupancy experiments only
@@ -2003,11 +2014,7 @@ int muavta_rollout_record(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, 
     e->err = "muavta_rollout_record: not available with the Cap-Greedy / PI allocators (set_allocator back to a Hungarian mode)";
     return MUAVTA_E_ARG;
   }
-  if (any_obs && n_steps > 0) {
-    DeviceScope scope_(e->device);
-    HIPCHK(e, hipMemsetAsync(rec->obs_done, MUAVTA_OBS_UNWRITTEN, (size_t)n_steps * (size_t)e->n_envs, e->stream));
-  }
-  return rollout_impl(e, seeds, n_steps, interval, use_vis, write_obs, rec);
+  return rollout_impl(e, seeds, n_steps, interval, use_vis, write_obs, rec);  // (pre-fills obs_done once the lane is chosen)
 }
 
 // ---- sub-batches ---------------------------------------------------------------------------------------------------------
@@ -2165,15 +2172,28 @@ int muavta_sync(MuavtaEnv* e) {
 
 int muavta_wait_stream(MuavtaEnv* e, void* other_stream) {  // work queued on the handle from now on starts after what `other_stream` holds now
   if (!e) return MUAVTA_E_ARG;
-  if (e->hl.twin) { int rc = muavta_wait_stream(e->hl.twin, other_stream); if (rc) { e->err = e->hl.twin->err; return rc; } }
   DeviceScope scope_(e->device);
   hipEvent_t ev = nullptr;
   HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   hipError_t r = hipEventRecord(ev, (hipStream_t)other_stream);
-  if (r == hipSuccess) r = hipStreamWaitEvent(e->stream, ev, 0);
-  // sub-batches: a part's stream is ordered after the main stream's work at its next launch (fork_part), so the wait carries over
-  for (int p = 0; p < e->n_parts; p++) e->part_fork_needed[p] = true;
-  hipEventDestroy(ev);  // (destruction is deferred by the runtime until the event has completed)
+  for (MuavtaEnv* L : {e, e->hl.twin}) {  // both lanes
+    if (!L || r != hipSuccess) continue;
+    r = hipStreamWaitEvent(L->stream, ev, 0);
+    // sub-batches: a part's stream is ordered after the main stream's work at its next launch (fork_part), so the wait carries over
+    for (int p = 0; p < L->n_parts; p++) L->part_fork_needed[p] = true;
+  }
+  if (r == hipSuccess && !e->hl.twin) {
+    // no second lane yet: ensure_twin makes one created later wait on the event too.  Events whose work has completed order
+    // nothing any more and are dropped here, so a caller that never gets a second lane keeps only the waits still in flight.
+    auto& pw = e->hl.pending_waits;
+    size_t k = 0;
+    for (hipEvent_t w : pw) { if (hipEventQuery(w) == hipSuccess) hipEventDestroy(w); else pw[k++] = w; }
+    (void)hipGetLastError();
+    pw.resize(k);
+    pw.push_back(ev);
+    ev = nullptr;
+  }
+  if (ev) hipEventDestroy(ev);  // (destruction is deferred by the runtime until the event has completed)
   if (r != hipSuccess) { e->err = std::string("muavta_wait_stream: ") + hipGetErrorString(r); return MUAVTA_E_HIP; }
   return MUAVTA_OK;
 }

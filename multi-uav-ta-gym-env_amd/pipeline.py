@@ -52,15 +52,22 @@ class InFlightRollouts:
 
     def results(self, all_pending: bool = False) -> Iterator[Tuple[object, np.ndarray]]:
         """(tag, metrics [n_envs, 30]) of the oldest queued batch — or of every queued batch, oldest first.  Blocks for each.
-        An env that overflowed its tile fails the batch loudly, as `metrics()` does; the batch stays queued in that case."""
+        An env that overflowed its tile fails the batch loudly, as `metrics()` does: the MuavtaError carries the batch's `tag`, its
+        `metrics` and its `error_flags` [n_envs] (nonzero rows are not results).  The failed batch has left the queue by then, so the
+        caller recovers by handling the error (e.g. re-running those seeds with `rollout(escalate=True)`) and calling `results()` /
+        `submit()` again: the batches queued behind it are intact."""
         while self._pending:
             k, tag = self._pending[0]
             e = self.envs[k]
             back = sum(1 for h, _ in self._pending if h == k) - 1  # batches this handle launched after the one asked for: 0 or 1
             m = e.rollout_metrics(back=back)  # (synchronises that lane's stream)
-            if np.count_nonzero(e.error_flags(back=back)):
-                raise MuavtaError("an env of the batch overflowed its tile (muavta_get ERROR): use BatchedMultiUAVEnv.rollout(escalate=True) for such workloads")
+            flags = e.error_flags(back=back)
             self._pending.popleft()
+            if np.count_nonzero(flags):
+                err = MuavtaError(f"an env of batch {tag!r} overflowed its tile (muavta_get ERROR): use BatchedMultiUAVEnv.rollout(escalate=True) "
+                                  "for such workloads")
+                err.tag, err.metrics, err.error_flags = tag, m, flags
+                raise err
             yield tag, m
             if not all_pending:
                 return
