@@ -237,9 +237,40 @@ int muavta_step_staged(MuavtaEnv* env); /* step with the actions muavta_allocate
  *   included.  use_visibility=0 passes agent_known_ids=None.
  *   Both run in kernel instantiations of their own.  muavta_rollout_record returns MUAVTA_E_ARG in these two modes; the IL / RL
  *   entry points (muavta_allocate_scored, muavta_rl_step, muavta_rl_run) run their own planners whatever the mode. */
+/*   MUAVTA_ALLOC_MLP_PAIR = MLP-Pair, the learned pair-cost hybrid without attention: PairCostHybrid(use_attention=False).plan(env,
+ *   hung, events, force=True) under _should_replan(env, events, replan_interval) — tok = build_pair_tokens(env, 32, 16, raw=raw_features),
+ *   scores = tanh(pair_mlp(cat([agent_feats[i], task_feats[j]]))) * score_clamp * edge_valid, then allocate_tasks(edge_scores=...) as
+ *   MUAVTA_ALLOC_URGENCY_PAIR does with its engineered score (TaskAllocation/Hybrid/PairCostHybrid.py:154-197,266-278,308-328;
+ *   experiments/wps_eval.py:244-254,490-492 with interval 15; train_pair_cost.py:73-93 with 20).  The plan is muavta_allocate_scored's
+ *   with kind = MUAVTA_TOK_PAIR(_RAW), max_agents 16, max_tasks 32, MUAVTA_SC_EDGE_VALID_ONLY, MUAVTA_GATE_TRAINER; n_replans counts the
+ *   HungarianAllocator's plans, as in MUAVTA_ALLOC_URGENCY_PAIR.  Needs muavta_set_pair_policy first (else MUAVTA_E_STATE); kernel
+ *   instantiations of its own; muavta_rollout_record returns MUAVTA_E_ARG.  Attention nets (AttPairNet), exploration noise and the
+ *   value head are out of scope. */
 enum { MUAVTA_ALLOC_HUNGARIAN = 0, MUAVTA_ALLOC_URGENCY_PAIR = 1, MUAVTA_ALLOC_URGENCY_COALITION = 2, MUAVTA_ALLOC_HUNGARIAN_GATED = 3,
-       MUAVTA_ALLOC_CAP_GREEDY = 4, MUAVTA_ALLOC_PI = 5 };
+       MUAVTA_ALLOC_CAP_GREEDY = 4, MUAVTA_ALLOC_PI = 5, MUAVTA_ALLOC_MLP_PAIR = 6 };
 int muavta_set_allocator(MuavtaEnv* env, int32_t mode);
+
+/* The network of MUAVTA_ALLOC_MLP_PAIR: pair_mlp = Linear(K, hidden) - ReLU - Linear(hidden, hidden) - ReLU - Linear(hidden, 1) with
+ * K = 12 + 13 (raw_features: 11 + 9).  HOST pointers in state_dict layout ([out, in] row-major): w0 [hidden, K], b0 [hidden],
+ * w1 [hidden, hidden], b1 [hidden], w2 [1, hidden], b2 [1].  hidden must be 128 (the reference's; anything else: MUAVTA_E_ARG).
+ * muavta_set_pair_policy copies the weights (the caller's arrays are free again when it returns), is ordered behind every launch
+ * already queued on the handle (both state lanes, sub-batch streams) and synchronises; a second call replaces the policy, NULL clears
+ * it (MUAVTA_E_STATE while MUAVTA_ALLOC_MLP_PAIR is selected).
+ * ARITHMETIC (the device's definition; torch's summation order is unspecified): every Linear output is one k-ascending float32 fmaf
+ * chain that starts from the bias — acc = b[n]; for k = 0..K-1: acc = fmaf(W[n][k], x[k], acc) — over x = the agent row's features
+ * followed by the task row's; ReLU = (acc > 0 ? acc : 0); score = tanhf(logit) * score_clamp.  A logit depends on its K inputs and the
+ * weights only: equal token rows give bit-equal scores.  Pairs whose edge_valid is 0 are not evaluated.
+ * muavta_pair_scores: scores / logits f32 [N, 16, 32] of every env's CURRENT state (build_pair_tokens(env, 32, 16) + the forward pass,
+ * the code the allocator mode runs at a replan); 0 where edge_valid is 0; either may be NULL.  Host buffers, synchronises.
+ * muavta_pair_scores_device: device buffers, on the handle's stream, no synchronisation. */
+typedef struct MuavtaPairMlp {
+  int32_t raw_features, hidden;
+  float score_clamp;
+  const float *w0, *b0, *w1, *b1, *w2, *b2;
+} MuavtaPairMlp;
+int muavta_set_pair_policy(MuavtaEnv* env, const MuavtaPairMlp* spec);
+int muavta_pair_scores(MuavtaEnv* env, float* scores, float* logits);
+int muavta_pair_scores_device(MuavtaEnv* env, float* scores, float* logits);
 
 /* Token builders of the learned/engineered hybrids, batched over all envs straight from the device state
  * (SURVEY §8f rank 2).  kind:

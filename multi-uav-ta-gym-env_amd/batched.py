@@ -119,10 +119,110 @@ class BatchedMultiUAVEnv:
         or one of the classical baselines: 'cap_greedy' (Local-Cap-Greedy: CapabilityGreedy's one best pair at every step,
         experiments/wps_eval.py:160-167; replan_interval is ignored) or 'pi' (Local-PI: PerformanceImpact with
         max_tasks_per_agent=1 under its own should_replan gate, replan_interval = its interval; wps_eval.py:147-159).  In the
-        two baseline modes rollout_record raises MuavtaError."""
-        self._alloc_mode = {"hungarian": 0, "urgency_pair": 1, "urgency_coalition": 2, "hungarian_gated": 3,
-                            "cap_greedy": 4, "pi": 5}[name]
-        self._ck(self.L.muavta_set_allocator(self.h, self._alloc_mode))
+        two baseline modes rollout_record raises MuavtaError.
+        'mlp_pair' (MLP-Pair: PairCostHybrid(use_attention=False).plan under _should_replan(env, events, replan_interval), the
+        network's forward pass inside the kernel; wps_eval.py:244-254 with interval 15, train_pair_cost.py:73-93 with 20) needs
+        `set_pair_policy` first; rollout_record raises MuavtaError in it too."""
+        mode = self.ALLOCATORS[name]
+        self._ck(self.L.muavta_set_allocator(self.h, mode))
+        self._alloc_mode = mode
+
+    ALLOCATORS = {"hungarian": 0, "urgency_pair": 1, "urgency_coalition": 2, "hungarian_gated": 3, "cap_greedy": 4, "pi": 5, "mlp_pair": 6}
+    PAIR_MLP_KEYS = tuple(f"pair_mlp.{i}.{k}" for i in (0, 2, 4) for k in ("weight", "bias"))
+
+    @classmethod
+    def parse_pair_policy(cls, src, score_clamp: Optional[float] = None):
+        """The MLP-Pair network of `src` as {'w0','b0','w1','b1','w2','b2': C-contiguous float32 arrays in state_dict layout,
+        'raw_features': bool, 'score_clamp': float, 'hidden': int}.  `src`: a path to a PairCostHybrid.save checkpoint (torch is
+        imported only then), a state_dict-like mapping with pair_mlp.{0,2,4}.{weight,bias} (torch tensors or arrays; an optional
+        'raw_features' / 'score_clamp' entry is honoured; a mapping with a 'state_dict' entry is a loaded checkpoint), or a PairCostHybrid.
+        Attention checkpoints (use_attention=True / AttPairNet) are refused.  Needs no device."""
+        import os
+        raw, clamp, sd = None, None, None
+        if isinstance(src, (str, bytes, os.PathLike)):
+            import torch
+            try:  # PairCostHybrid.save writes a plain dict of tensors and scalars: nothing in it needs the unpickler to run code
+                src = torch.load(src, map_location="cpu", weights_only=True)
+            except Exception as exc:
+                raise ValueError(f"set_pair_policy: {src!r} is not a checkpoint of tensors and plain values (torch.load(weights_only=True): {exc}); "
+                                 "load it yourself and pass the state_dict") from exc
+        if hasattr(src, "net") and hasattr(src, "use_attention"):  # a PairCostHybrid
+            if src.use_attention:
+                raise ValueError("set_pair_policy: use_attention=True (AttPairNet) is not supported; only the MLP variant runs on the device")
+            raw, clamp, sd = bool(src.raw_features), float(src.score_clamp), src.net.state_dict()
+        elif hasattr(src, "keys") and "state_dict" in src.keys():  # what PairCostHybrid.save writes (PairCostHybrid.py:469-485)
+            if src.get("use_attention", False):
+                raise ValueError("set_pair_policy: the checkpoint was saved with use_attention=True (AttPairNet); only the MLP variant runs on the device")
+            raw, sd = bool(src.get("raw_features", False)), src["state_dict"]
+            clamp = float(src["score_clamp"]) if "score_clamp" in src.keys() else None
+        elif hasattr(src, "keys"):
+            sd = src
+            if "raw_features" in sd.keys():
+                raw = bool(np.asarray(sd["raw_features"]).reshape(-1)[0])
+            if "score_clamp" in sd.keys():
+                clamp = float(np.asarray(sd["score_clamp"]).reshape(-1)[0])
+        else:
+            raise ValueError("set_pair_policy: expected a checkpoint path, a state_dict-like mapping or a PairCostHybrid")
+        missing = [k for k in cls.PAIR_MLP_KEYS if k not in sd.keys()]
+        if missing:
+            att = any(str(k).startswith(("encoder", "task_proj", "agent_proj", "cross")) for k in sd.keys())
+            raise ValueError(f"set_pair_policy: no {missing[0]} in the weights" + (" (an attention net? only the MLP variant is supported)" if att else ""))
+
+        def arr(k):
+            v = sd[k]
+            if hasattr(v, "detach"):
+                v = v.detach().cpu().numpy()
+            return np.ascontiguousarray(v, dtype=np.float32)
+        w0, b0, w1, b1, w2, b2 = (arr(k) for k in cls.PAIR_MLP_KEYS)
+        hidden = b0.shape[0] if b0.ndim == 1 else -1
+        if w0.ndim != 2 or w0.shape[1] not in (20, 25) or (raw is not None and w0.shape[1] != (20 if raw else 25)):
+            raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {w0.shape}; expected [hidden, 25] (raw_features: [hidden, 20])")
+        raw = w0.shape[1] == 20
+        want = {"pair_mlp.0.weight": (hidden, w0.shape[1]), "pair_mlp.0.bias": (hidden,), "pair_mlp.2.weight": (hidden, hidden),
+                "pair_mlp.2.bias": (hidden,), "pair_mlp.4.weight": (1, hidden), "pair_mlp.4.bias": (1,)}
+        for k, a in zip(cls.PAIR_MLP_KEYS, (w0, b0, w1, b1, w2, b2)):
+            if a.shape != want[k]:
+                raise ValueError(f"set_pair_policy: {k} has shape {a.shape}; expected {want[k]}")
+        if hidden != 128:
+            raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's hidden = 128 only")
+        if score_clamp is not None:
+            clamp = float(score_clamp)
+        if clamp is None:
+            clamp = 0.35  # SCORE_CLAMP (PairCostHybrid.py): the value every checkpoint of the reference is trained and saved with
+        return {"w0": w0, "b0": b0, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "raw_features": raw, "score_clamp": clamp, "hidden": hidden}
+
+    def set_pair_policy(self, src, score_clamp: Optional[float] = None):
+        """muavta_set_pair_policy: the network `set_allocator('mlp_pair')` and `pair_scores` run (see `parse_pair_policy` for `src`;
+        None clears it).  The weights are copied; a second call replaces them, also between rollouts."""
+        if src is None:
+            self._ck(self.L.muavta_set_pair_policy(self.h, None))
+            self._pair_policy = None
+            return
+        pol = self.parse_pair_policy(src, score_clamp)
+        spec = native.MuavtaPairMlp(int(pol["raw_features"]), int(pol["hidden"]), float(pol["score_clamp"]),
+                                    *(pol[k].ctypes.data for k in ("w0", "b0", "w1", "b1", "w2", "b2")))
+        self._ck(self.L.muavta_set_pair_policy(self.h, C.byref(spec)))
+        self._pair_policy = pol
+
+    def pair_scores(self, out=None, want_logits: bool = False):
+        """muavta_pair_scores: the policy's scores (and logits) f32 [N, 16, 32] of every env's current state, 0 where edge_valid
+        is 0.  numpy by default (synchronises); `out` = {'scores': t[, 'logits': t]} of contiguous CUDA torch tensors goes through
+        the device entry on the handle's stream without a sync and is returned."""
+        shape = (self.n_envs, 16, 32)
+        if out is not None:
+            if not out:
+                raise ValueError("pair_scores: out must hold a 'scores' and / or a 'logits' tensor")
+            for name, t in out.items():
+                if name not in ("scores", "logits") or tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float32" \
+                        or t.device.index != self.device_index:
+                    raise ValueError(f"pair_scores: out['scores' / 'logits'] must be contiguous float32 tensors of shape {shape} on cuda:{self.device_index}")
+            s, lg = out.get("scores"), out.get("logits")
+            self._ck(self.L.muavta_pair_scores_device(self.h, None if s is None else s.data_ptr(), None if lg is None else lg.data_ptr()))
+            return out
+        scores = np.empty(shape, dtype=np.float32)
+        logits = np.empty(shape, dtype=np.float32) if want_logits else None
+        self._ck(self.L.muavta_pair_scores(self.h, _fp(scores), None if logits is None else _fp(logits)))
+        return (scores, logits) if want_logits else scores
 
     GATES = {"force": 0, "trainer": 1, "escort": 2, "allocator": 3}
     SC_EDGE_VALID_ONLY, SC_FULL_TASK_LIST, SC_COMMIT = 1, 2, 4
@@ -418,6 +518,10 @@ class BatchedMultiUAVEnv:
                 p.tile_agents, p.tile_tasks, p.tile_threats = a, t, max(hh, self.H)
                 h = BatchedMultiUAVEnv(p, max(len(idx), 64), device=self.device_index)
                 self._esc_handles[rung] = h
+            if getattr(self, "_pair_policy", None) is not None and getattr(h, "_pair_policy_from", None) is not self._pair_policy:  # (new handle, or the policy changed since)
+                h.set_pair_policy({**{k: self._pair_policy[w] for k, w in zip(self.PAIR_MLP_KEYS, ("w0", "b0", "w1", "b1", "w2", "b2"))},
+                                   "raw_features": self._pair_policy["raw_features"]}, self._pair_policy["score_clamp"])
+                h._pair_policy_from = self._pair_policy
             h._ck(h.L.muavta_set_allocator(h.h, self._alloc_mode))
             s2 = np.full(h.n_envs, seeds[idx[0]], dtype=np.uint64)
             s2[:len(idx)] = seeds[idx]

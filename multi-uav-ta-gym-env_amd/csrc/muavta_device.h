@@ -132,6 +132,25 @@ struct ScoredDev {
   int32_t kind, MT, MA, gate, flags;
 };
 
+// muavta_set_pair_policy: the MLP-Pair network (PairCostHybrid.pair_mlp, use_attention=False) and the per-env token / score scratch of
+// the MUAVTA_ALLOC_MLP_PAIR mode.  Weights: ONE packed f32 buffer per lane, laid out for the order the forward pass streams them through
+// the scalar cache in: layer 1 k-major (W0T[k][n]: its loop runs k outside, 64 outputs inside); layer 2 in groups of four outputs with
+// their weights interleaved ([n / 4][k][n % 4]: the four chains that run side by side read one k of each from neighbouring words);
+// layer 3 and the biases as they are.  See sim/policy.inc.
+struct PairPolicyDev {
+  const float* w;    // [PW_FLOATS], null: no policy set
+  float* scratch;    // [N][PS_FLOATS]
+  int32_t raw;       // checkpoint's raw_features: tokens of kind MUAVTA_TOK_PAIR_RAW (agent 11 + task 9) instead of MUAVTA_TOK_PAIR (12 + 13)
+  float clamp;       // score_clamp
+};
+enum { PW_HID = 128, PW_W0_ROWS = 25,
+       PW_W0 = 0, PW_B0 = PW_W0 + PW_HID * PW_W0_ROWS, PW_W1 = PW_B0 + PW_HID, PW_B1 = PW_W1 + PW_HID * PW_HID, PW_W2 = PW_B1 + PW_HID,
+       PW_B2 = PW_W2 + PW_HID, PW_FLOATS = PW_B2 + 16 };
+// per-env scratch, in floats: the token tensors build_pair_tokens(env, 32, 16) of the plan being made, and its scores
+enum { PS_MA = 16, PS_MT = 32,
+       PS_TF = 0, PS_AF = PS_TF + PS_MT * 13, PS_EV = PS_AF + PS_MA * 12, PS_SCORES = PS_EV + PS_MA * PS_MT, PS_TID = PS_SCORES + PS_MA * PS_MT,
+       PS_AID = PS_TID + PS_MT, PS_TMASK = PS_AID + PS_MA, PS_AMASK = PS_TMASK + PS_MT / 4, PS_FLOATS = (PS_AMASK + PS_MA / 4 + 3) & ~3 };
+
 template <class TL>
 struct Sim {
   typedef EnvState<TL> State;
@@ -201,6 +220,7 @@ struct Sim {
 #include "sim/allocate.inc"
 #include "sim/baselines.inc"
 #include "sim/tokens.inc"
+#include "sim/policy.inc"
 #include "sim/lsap.inc"
 #include "sim/metrics.inc"
 };

@@ -55,6 +55,7 @@ struct DevCtx {
   void* blobs;      // EnvState<TL>[N]: the LDS image of every env between launches
   void* cold;       // EnvCold<TL>[N]: the HBM-only part of every env
   uint32_t* pace;   // [PACE_KEYS][16] step counters of the waves resident on each SIMD (k_rollout's issue-priority pacing)
+  PairPolicyDev pol;  // muavta_set_pair_policy (rewritten on the handle's stream; all zero: no policy).  Last: nothing in front of it moves
 };
 enum { PACE_KEYS = 1 << 16 };  // (XCC_ID[3:0], HW_ID[15:4] = se, sh, cu, pipe, simd)
 // the context as uniform constant memory: scalar loads, hoistable across the phase barriers
@@ -287,8 +288,10 @@ __global__ __launch_bounds__(WG, TILE_MIN_WAVES(TL)) void k_step(const DevCtx* _
   copy16(blob, L.S, sizeof(EnvState<TL>));
 }
 
+enum { SCORED_EXTRA_LDS = 128 };  // allocate<true>'s task list: one byte per slot, behind the tile
 // BL: the classical baselines (MUAVTA_ALLOC_CAP_GREEDY, MUAVTA_ALLOC_PI; sim/baselines.inc) in instantiations of their own
-template <class TL, bool BL = false>
+// PM: the learned MLP-Pair hybrid (MUAVTA_ALLOC_MLP_PAIR; sim/policy.inc), likewise; launched with SCORED_EXTRA_LDS bytes behind the tile
+template <class TL, bool BL = false, bool PM = false>
 __global__ __launch_bounds__(WG) void k_allocate(const DevCtx* __restrict__ ctxp, int interval, int use_vis, int mode,
                                                  int32_t* out_agent, int32_t* out_index, int act_cap, int env_base) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -298,7 +301,8 @@ __global__ __launch_bounds__(WG) void k_allocate(const DevCtx* __restrict__ ctxp
   copy16(L.S, blob, sizeof(EnvState<TL>));
   lds_sync();
   Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, tape_of(ctx, env));
-  if constexpr (BL) sim.allocate_baseline(interval, use_vis, mode);
+  if constexpr (PM) sim.allocate_mlp(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PS_FLOATS, smem + Lds<TL>::bytes());
+  else if constexpr (BL) sim.allocate_baseline(interval, use_vis, mode);
   else sim.allocate(interval, use_vis, mode);
   lds_sync();
   if (out_agent) {
@@ -322,7 +326,6 @@ __device__ __forceinline__ typename Sim<TL>::TokPtrs global_tok_ptrs(typename Si
 
 // muavta_allocate_scored: k_allocate with the caller's edge scores / priorities / reserved agents (Sim::allocate<true>).  The
 // task list handed to the allocator sits in T bytes of LDS behind the tile.
-enum { SCORED_EXTRA_LDS = 128 };
 template <class TL>
 __global__ __launch_bounds__(WG) void k_allocate_scored(const DevCtx* __restrict__ ctxp, ScoredDev sc, int interval, int use_vis,
                                                         int32_t* out_agent, int32_t* out_index, int act_cap, int env_base) {
@@ -525,7 +528,7 @@ struct RecordPtrs {
 struct RecBlob { uint32_t w[64]; };  // 256 B: a RecordPtrs<TL> by value
 __global__ void k_store_rec(RecBlob b, uint32_t* dst) { dst[threadIdx.x] = b.w[threadIdx.x]; }
 
-template <class TL, bool REC, bool BL = false>
+template <class TL, bool REC, bool BL = false, bool PM = false>
 __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned char* lds_own, uint32_t lds_base, int env, int phases, int interval, int use_vis, int mode,
                                                 const RecordPtrs<TL>& rec, int slot, int oslot) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -552,7 +555,9 @@ __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned cha
   }
   lds_sync();
   if (!ABL(9) && (phases & PH_ALLOC) && !(L.S->terminated || L.S->truncated)) {
-    if constexpr (BL) sim.allocate_baseline(interval, use_vis, mode);
+    if constexpr (PM) sim.allocate_mlp(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PS_FLOATS,
+                                       reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS);
+    else if constexpr (BL) sim.allocate_baseline(interval, use_vis, mode);
     else sim.allocate(interval, use_vis, mode);
     if (REC && rec.K.task_feats) {  // the sample of step `slot`: tokens + labels of the plan just staged, S_WPS before the step
       const typename Sim<TL>::TokPtrs K = global_tok_ptrs<TL>(rec.K);
@@ -565,8 +570,10 @@ __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned cha
   PROF_AT(sim, 20);
 }
 
-template <class TL, bool REC, bool BL = false>
-__global__ __launch_bounds__(WG, TILE_MIN_WAVES(TL)) void k_rollout(const DevCtx* __restrict__ ctxp, const uint64_t* seeds, int n_steps, int interval, int use_vis,
+// (PM: the forward pass keeps a pair's 128 hidden activations in registers, ~145 VGPRs — those instantiations are built for three waves
+// per SIMD, 168 VGPRs, where the tile's other kernels are built for four)
+template <class TL, bool REC, bool BL = false, bool PM = false>
+__global__ __launch_bounds__(WG, PM ? (TILE_MIN_WAVES(TL) < 3 ? TILE_MIN_WAVES(TL) : 3) : TILE_MIN_WAVES(TL)) void k_rollout(const DevCtx* __restrict__ ctxp, const uint64_t* seeds, int n_steps, int interval, int use_vis,
                                                 int mode, int write_obs, double* metrics, const uint32_t* seedbuf, const RecordPtrs<TL>* __restrict__ recp, int epoch, int env_base) {
   const DevCtx& ctx = ctx_ref(ctxp);
   // The ring pointers of muavta_rollout_record sit in device memory (one slot per handle, written on the launch's stream just ahead of
@@ -577,7 +584,7 @@ __global__ __launch_bounds__(WG, TILE_MIN_WAVES(TL)) void k_rollout(const DevCtx
   // (unsigned halves: v_readfirstlane returns int, and a low word with bit 31 set would sign-extend into the high word)
   const RecordPtrs<TL>& rec = *(const RecordPtrs<TL>*)(const AS4 RecordPtrs<TL>*)(((uint64_t)rec_hi << 32) | (uint64_t)rec_lo);
   const int env = env_base + blockIdx.x;
-  KERNEL_LDS(TL);
+  __shared__ __align__(16) unsigned char lds_own[Lds<TL>::bytes() + PROF_EXTRA_LDS + (PM ? SCORED_EXTRA_LDS : 0)];  // KERNEL_LDS(TL) (+ PM: allocate<true>'s task list)
   Lds<TL> L(lds_own);
   EnvState<TL>* blob = blob_of<TL>(ctx, env);
   Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, tape_of(ctx, env));
@@ -659,7 +666,7 @@ static_assert(MUAVTA_PACE_HOLD_POLLS > 0 && MUAVTA_PACE_HOLD_POLLS <= (1 << 16),
       if (threadIdx.x < 16) seen = __hip_atomic_load(pace_row + threadIdx.x, __ATOMIC_RELAXED, MUAVTA_PACE_SCOPE);
     }
 #endif
-    if (ph) rollout_phase<TL, REC, BL>(ctxp, lds_own, lds_base, env, ph, interval, use_vis, mode, rec, k < n_steps ? k : n_steps,
+    if (ph) rollout_phase<TL, REC, BL, PM>(ctxp, lds_own, lds_base, env, ph, interval, use_vis, mode, rec, k < n_steps ? k : n_steps,
                                    (REC && rec.O.tasks && k >= 1 && k <= n_steps) ? k - 1 : -1);
 #if MUAVTA_PACE_PRIO
     if (PACED && k >= 1 && k <= n_steps && (k & (MUAVTA_PACE_EVERY - 1)) == 0) {  // consumed a step later: the load's latency stays off the env's dependent chain
@@ -753,6 +760,24 @@ __global__ __launch_bounds__(WG) void k_tokens(const DevCtx* __restrict__ ctxp, 
   lds_sync();
   Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, nullptr);
   sim.tokens(K, env);
+}
+
+// muavta_pair_scores(_device): the MLP-Pair policy's scores / logits of every env's CURRENT state — build_pair_tokens(env, 32, 16) into
+// the env's scratch block, then the forward pass of sim/policy.inc, the same code the MUAVTA_ALLOC_MLP_PAIR mode runs at a replan.
+// scores / logits: [N, 16, 32] (either may be null); entries whose edge_valid is 0 are written as 0.  The env records are not changed.
+template <class TL>
+__global__ __launch_bounds__(WG) void k_pair_scores(const DevCtx* __restrict__ ctxp, float* scores, float* logits) {
+  const DevCtx& ctx = ctx_ref(ctxp);
+  const int env = blockIdx.x;
+  Lds<TL> L(smem);
+  copy16(L.S, blob_of<TL>(ctx, env), sizeof(EnvState<TL>));
+  lds_sync();
+  Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, nullptr);
+  float* scratch = as_global(ctx.pol.scratch) + (size_t)env * PS_FLOATS;
+  sim.pair_tokens_scratch(ctx.pol, scratch);
+  const size_t at = (size_t)env * PS_MA * PS_MT;
+  sim.pair_forward(ctx.pol, scratch + PS_TF, scratch + PS_AF, scratch + PS_EV, scores ? as_global(scores) + at : nullptr,
+                   logits ? as_global(logits) + at : nullptr, true);
 }
 
 template <class TL>
@@ -994,6 +1019,7 @@ struct MuavtaEnv {
   int comm_rank = 0, comm_ranks = 0;
   void* d_comm = nullptr;     // [64 f64 send | 64 x n_ranks f64 recv | 64 i64 send | 64 i64 recv]
   double* d_metrics = nullptr;
+  float *d_pol_w = nullptr, *d_pol_scratch = nullptr;  // muavta_set_pair_policy: this lane's copy of the packed weights, its per-env token / score scratch
   ObsPtrs O{};
   hipStream_t stream = nullptr;
   // sub-batches (muavta_set_parts): contiguous env ranges, each stepped on its own stream so that the host can decide for one part
@@ -1032,6 +1058,11 @@ struct MuavtaEnv {
     unsigned long long ring_no[RING] = {};      // ... as that lane's launch number
     unsigned long long n_launches = 0;
     std::vector<hipEvent_t> pending_waits;  // muavta_wait_stream events recorded while there was no second lane: one created later waits on them
+    // muavta_set_pair_policy: the packed weights (PW_* layout) as the caller last set them — a second lane created later gets its copy from here
+    std::vector<float> pol_w;
+    int pol_raw = 0;
+    float pol_clamp = 0.f;
+    bool pol_set = false;
   } hl;
 };
 static int join_parts(MuavtaEnv* e);  // (sub-batches: defined with the other part helpers in front of the C ABI)
@@ -1040,6 +1071,7 @@ extern "C" int muavta_set_release_log(MuavtaEnv* e, int32_t enable);
 extern "C" int muavta_create(const MuavtaParams* params, int32_t n_envs, int32_t device, MuavtaEnv** out);
 extern "C" int muavta_destroy(MuavtaEnv* e);
 extern "C" int muavta_set_slot_cap(MuavtaEnv* e, int32_t cap);
+static int push_policy(MuavtaEnv* lane, const MuavtaEnv::HandleLevel& hl);
 
 namespace {
 
@@ -1051,8 +1083,10 @@ int launch_attr(MuavtaEnv* e) {
     const void* ks[] = {reinterpret_cast<const void*>(&k_reset<TL>), reinterpret_cast<const void*>(&k_step<TL>), reinterpret_cast<const void*>(&k_allocate<TL>),
                         reinterpret_cast<const void*>(&k_rollout<TL, false>), reinterpret_cast<const void*>(&k_rollout<TL, true>), reinterpret_cast<const void*>(&k_metrics<TL>), reinterpret_cast<const void*>(&k_observe<TL>),
                         reinterpret_cast<const void*>(&k_tokens<TL>), reinterpret_cast<const void*>(&k_call<TL>), reinterpret_cast<const void*>(&k_context<TL>),
-                        reinterpret_cast<const void*>(&k_allocate<TL, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, true>)};
+                        reinterpret_cast<const void*>(&k_allocate<TL, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, true>),
+                        reinterpret_cast<const void*>(&k_pair_scores<TL>), reinterpret_cast<const void*>(&k_rollout<TL, false, false, true>)};
     for (const void* k : ks) HIPCHK(e, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate<TL, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
     HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate_scored<TL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
   }
   return MUAVTA_OK;
@@ -1436,6 +1470,7 @@ static int ensure_twin(MuavtaEnv* e) {  // create the second lane (same configur
   if (rc == MUAVTA_OK && e->d_rel) rc = muavta_set_release_log(t, 1);
   if (rc != MUAVTA_OK) { if (t) muavta_destroy(t); e->hl.twin_failed = true; return rc; }
   t->alloc_mode = e->alloc_mode;
+  if (e->hl.pol_set && push_policy(t, e->hl) != MUAVTA_OK) { e->err = t->err; muavta_destroy(t); e->hl.twin_failed = true; return MUAVTA_E_HIP; }
   if (e->P.slot_cap && muavta_set_slot_cap(t, e->P.slot_cap) != MUAVTA_OK) { muavta_destroy(t); e->hl.twin_failed = true; return MUAVTA_E_HIP; }
   // the waits the caller queued before this lane existed hold for it too (its part streams fork from its main stream at their first launch)
   for (hipEvent_t ev : e->hl.pending_waits)
@@ -1482,6 +1517,27 @@ static int check_part(MuavtaEnv* e, int p, const char* who) {
   if (!e) return MUAVTA_E_ARG;
   if (e->n_parts < 1 || p < 0 || p >= e->n_parts) { e->err = std::string(who) + ": no such part (muavta_set_parts first)"; return MUAVTA_E_ARG; }
   if (!e->did_reset) { e->err = std::string(who) + " before reset"; return MUAVTA_E_STATE; }
+  return MUAVTA_OK;
+}
+
+// muavta_set_pair_policy on ONE lane: the lane's copy of the weights, its scratch and the `pol` words of its context, on the lane's
+// stream behind whatever it (and its part streams) still runs; synchronised, so the host vector may change afterwards.
+static int push_policy(MuavtaEnv* l, const MuavtaEnv::HandleLevel& hl) {
+  DeviceScope scope_(l->device);
+  MAIN_OP(l);
+  PairPolicyDev pd;
+  memset(&pd, 0, sizeof(pd));
+  if (hl.pol_set) {
+    if (!l->d_pol_w) HIPCHK(l, hipMalloc((void**)&l->d_pol_w, (size_t)PW_FLOATS * sizeof(float)));
+    if (!l->d_pol_scratch) {
+      HIPCHK(l, hipMalloc((void**)&l->d_pol_scratch, (size_t)l->n_envs * PS_FLOATS * sizeof(float)));
+      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch, 0, (size_t)l->n_envs * PS_FLOATS * sizeof(float), l->stream));
+    }
+    HIPCHK(l, hipMemcpyAsync(l->d_pol_w, hl.pol_w.data(), (size_t)PW_FLOATS * sizeof(float), hipMemcpyHostToDevice, l->stream));
+    pd.w = l->d_pol_w; pd.scratch = l->d_pol_scratch; pd.raw = hl.pol_raw; pd.clamp = hl.pol_clamp;
+  }
+  HIPCHK(l, hipMemcpyAsync((char*)l->d_ctx + offsetof(DevCtx, pol), &pd, sizeof(pd), hipMemcpyHostToDevice, l->stream));
+  HIPCHK(l, hipStreamSynchronize(l->stream));  // `pd` is a stack object
   return MUAVTA_OK;
 }
 
@@ -1610,7 +1666,7 @@ int muavta_destroy(MuavtaEnv* e) {
   if (e->ev_fork) hipEventDestroy(e->ev_fork);
   hipFree(e->d_part_agent); hipFree(e->d_part_index); if (e->d_run) hipFree(e->d_run);
   if (e->stream) hipStreamSynchronize(e->stream);
-  if (e->d_seedtmp) hipFree(e->d_seedtmp); hipFree(e->blobs); hipFree(e->cold); hipFree(e->tapes); hipFree(e->d_ctx); hipFree(e->d_pace); if (e->d_rec) hipFree(e->d_rec); for (int b = 0; b < 2; b++) { hipFree(e->d_seeds[b]); if (e->d_seedbuf[b]) hipFree(e->d_seedbuf[b]); if (e->h_seeds[b]) hipHostFree(e->h_seeds[b]); } hipFree(e->d_act_agent); hipFree(e->d_act_index); if (e->d_list_agent) hipFree(e->d_list_agent); if (e->d_list_index) hipFree(e->d_list_index); hipFree(e->d_call_out); hipFree(e->d_metrics); if (e->d_tok) hipFree(e->d_tok); if (e->d_rel) hipFree(e->d_rel);
+  if (e->d_seedtmp) hipFree(e->d_seedtmp); hipFree(e->blobs); hipFree(e->cold); hipFree(e->tapes); hipFree(e->d_ctx); hipFree(e->d_pace); if (e->d_rec) hipFree(e->d_rec); for (int b = 0; b < 2; b++) { hipFree(e->d_seeds[b]); if (e->d_seedbuf[b]) hipFree(e->d_seedbuf[b]); if (e->h_seeds[b]) hipHostFree(e->h_seeds[b]); } hipFree(e->d_act_agent); hipFree(e->d_act_index); if (e->d_list_agent) hipFree(e->d_list_agent); if (e->d_list_index) hipFree(e->d_list_index); hipFree(e->d_call_out); hipFree(e->d_metrics); if (e->d_pol_w) hipFree(e->d_pol_w); if (e->d_pol_scratch) hipFree(e->d_pol_scratch); if (e->d_tok) hipFree(e->d_tok); if (e->d_rel) hipFree(e->d_rel);
   hipFree(e->O.tasks); hipFree(e->O.legal); hipFree(e->O.pad); hipFree(e->O.agents); hipFree(e->O.flags); hipFree(e->O.reward); hipFree(e->O.done);
   for (int i = 0; i < MuavtaEnv::EV_RING; i++) { if (e->ev0[i]) hipEventDestroy(e->ev0[i]); if (e->ev1[i]) hipEventDestroy(e->ev1[i]); }
   for (int b = 0; b < 2; b++) {
@@ -1743,7 +1799,10 @@ int muavta_allocate(MuavtaEnv* e, int32_t interval, int32_t use_vis, int32_t* ac
   if (!e->did_reset) { e->err = "allocate before reset"; return MUAVTA_E_STATE; }
   DeviceScope scope_(e->device);
   MAIN_OP(e);
-  if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY)
+  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR)
+    DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, false, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes() + SCORED_EXTRA_LDS, e->stream, (const DevCtx*)e->d_ctx,
+                                   interval, use_vis, e->alloc_mode, e->d_act_agent, e->d_act_index, e->A, 0))
+  else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY)
     DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, interval, use_vis,
                                    e->alloc_mode, e->d_act_agent, e->d_act_index, e->A, 0))
   else
@@ -1949,6 +2008,9 @@ static void launch_rollout(MuavtaEnv* e, const uint64_t* ds, int n_steps, int in
     hipLaunchKernelGGL(k_store_rec, dim3(1), dim3(64), 0, stream, blob, (uint32_t*)((char*)e->d_rec + MuavtaEnv::REC_SLOT));
     hipLaunchKernelGGL((k_rollout<TL, true>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
                        n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)((char*)e->d_rec + MuavtaEnv::REC_SLOT), epoch, env_base);
+  } else if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) {
+    hipLaunchKernelGGL((k_rollout<TL, false, false, true>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
+                       n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)e->d_rec, epoch, env_base);
   } else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) {
     hipLaunchKernelGGL((k_rollout<TL, false, true>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
                        n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)e->d_rec, epoch, env_base);
@@ -2011,7 +2073,9 @@ int muavta_rollout_record(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, 
     return MUAVTA_E_ARG;
   }
   if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) {  // the recording kernels carry the Hungarian-family planners only
-    e->err = "muavta_rollout_record: not available with the Cap-Greedy / PI allocators (set_allocator back to a Hungarian mode)";
+    e->err = e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR
+                 ? "muavta_rollout_record: not available with the MLP-Pair allocator (set_allocator back to a Hungarian mode)"
+                 : "muavta_rollout_record: not available with the Cap-Greedy / PI allocators (set_allocator back to a Hungarian mode)";
     return MUAVTA_E_ARG;
   }
   return rollout_impl(e, seeds, n_steps, interval, use_vis, write_obs, rec);  // (pre-fills obs_done once the lane is chosen)
@@ -2094,7 +2158,10 @@ int muavta_allocate_part(MuavtaEnv* e, int32_t part, int32_t interval, int32_t u
   int first, count;
   part_range(e, part, &first, &count);
   hipStream_t st = e->part_stream[part];
-  if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY)
+  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR)
+    DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, false, true>), dim3(count), dim3(WG), Lds<TL>::bytes() + SCORED_EXTRA_LDS, st, (const DevCtx*)e->d_ctx, interval, use_vis,
+                                   e->alloc_mode, e->d_part_agent, e->d_part_index, e->A, first))
+  else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY)
     DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, true>), dim3(count), dim3(WG), Lds<TL>::bytes(), st, (const DevCtx*)e->d_ctx, interval, use_vis,
                                    e->alloc_mode, e->d_part_agent, e->d_part_index, e->A, first))
   else
@@ -2155,9 +2222,98 @@ int muavta_prof_read(unsigned long long* out, int reset) {  // diagnostic build 
 #endif
 
 int muavta_set_allocator(MuavtaEnv* e, int32_t mode) {
-  if (!e || (mode < MUAVTA_ALLOC_HUNGARIAN || mode > MUAVTA_ALLOC_PI)) { if (e) e->err = "unknown allocator mode"; return MUAVTA_E_ARG; }
+  if (!e || (mode < MUAVTA_ALLOC_HUNGARIAN || mode > MUAVTA_ALLOC_MLP_PAIR)) { if (e) e->err = "unknown allocator mode"; return MUAVTA_E_ARG; }
+  if (mode == MUAVTA_ALLOC_MLP_PAIR && !e->hl.pol_set) {
+    e->err = "muavta_set_allocator: MUAVTA_ALLOC_MLP_PAIR needs a policy (muavta_set_pair_policy first)";
+    return MUAVTA_E_STATE;
+  }
   e->alloc_mode = mode;
   if (e->hl.twin) e->hl.twin->alloc_mode = mode;
+  return MUAVTA_OK;
+}
+
+// ---- the learned MLP-Pair hybrid (sim/policy.inc) ---------------------------------------------------------------------------------
+int muavta_set_pair_policy(MuavtaEnv* e, const MuavtaPairMlp* spec) {
+  if (!e) return MUAVTA_E_ARG;
+  // what the handle holds now: put back if the new policy does not reach BOTH lanes (the handle-level record must never say "set"
+  // while a lane's context holds no, or another, policy)
+  std::vector<float> old_w = e->hl.pol_w;
+  const int old_raw = e->hl.pol_raw;
+  const float old_clamp = e->hl.pol_clamp;
+  const bool old_set = e->hl.pol_set;
+  if (!spec) {  // clear
+    if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) {
+      e->err = "muavta_set_pair_policy: the MLP-Pair allocator is selected; muavta_set_allocator to another mode before clearing its policy";
+      return MUAVTA_E_STATE;
+    }
+    e->hl.pol_set = false;
+    e->hl.pol_w.clear();
+  } else {
+    if (spec->hidden != PW_HID || (spec->raw_features != 0 && spec->raw_features != 1) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 || !spec->w2 ||
+        !spec->b2 || !(spec->score_clamp == spec->score_clamp)) {
+      e->err = "muavta_set_pair_policy: bad spec (hidden must be 128, raw_features 0 or 1, six non-null arrays, score_clamp a number)";
+      return MUAVTA_E_ARG;
+    }
+    const int k0 = spec->raw_features ? 20 : 25;
+    std::vector<float> w((size_t)PW_FLOATS, 0.f);
+    for (int n = 0; n < PW_HID; n++)
+      for (int k = 0; k < k0; k++) w[PW_W0 + (size_t)k * PW_HID + n] = spec->w0[(size_t)n * k0 + k];  // k-major on the device
+    memcpy(&w[PW_B0], spec->b0, PW_HID * sizeof(float));
+    for (int n = 0; n < PW_HID; n++)
+      for (int k = 0; k < PW_HID; k++) w[PW_W1 + ((size_t)(n / 4) * PW_HID + k) * 4 + n % 4] = spec->w1[(size_t)n * PW_HID + k];  // four outputs interleaved
+    memcpy(&w[PW_B1], spec->b1, PW_HID * sizeof(float));
+    memcpy(&w[PW_W2], spec->w2, PW_HID * sizeof(float));
+    w[PW_B2] = spec->b2[0];
+    e->hl.pol_w.swap(w);
+    e->hl.pol_raw = spec->raw_features; e->hl.pol_clamp = spec->score_clamp; e->hl.pol_set = true;
+  }
+  int rc = push_policy(e, e->hl);
+  if (rc == MUAVTA_OK && e->hl.twin) { rc = push_policy(e->hl.twin, e->hl); if (rc) e->err = e->hl.twin->err; }
+  if (rc == MUAVTA_OK) return MUAVTA_OK;
+  const std::string why = e->err;
+  e->hl.pol_w.swap(old_w); e->hl.pol_raw = old_raw; e->hl.pol_clamp = old_clamp; e->hl.pol_set = old_set;
+  int back = push_policy(e, e->hl);
+  if (back == MUAVTA_OK && e->hl.twin) back = push_policy(e->hl.twin, e->hl);
+  if (back != MUAVTA_OK) {  // not even the previous policy could be put back: no policy, and no mode that needs one
+    e->hl.pol_set = false;
+    e->hl.pol_w.clear();
+    if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) { e->alloc_mode = MUAVTA_ALLOC_HUNGARIAN; if (e->hl.twin) e->hl.twin->alloc_mode = MUAVTA_ALLOC_HUNGARIAN; }
+    e->err = "muavta_set_pair_policy failed (" + why + ") and the previous policy could not be restored: the handle has no policy now and runs the Hungarian allocator";
+    return rc;
+  }
+  e->err = "muavta_set_pair_policy failed, the previous policy is kept: " + why;
+  return rc;
+}
+int muavta_pair_scores_device(MuavtaEnv* e, float* scores, float* logits) {
+  if (!e) return MUAVTA_E_ARG;
+  if (!e->hl.pol_set) { e->err = "muavta_pair_scores: no policy (muavta_set_pair_policy first)"; return MUAVTA_E_STATE; }
+  if (!e->did_reset) { e->err = "muavta_pair_scores before reset"; return MUAVTA_E_STATE; }
+  if (!scores && !logits) return MUAVTA_OK;
+  DeviceScope scope_(e->device);
+  MAIN_OP(e);
+  DISPATCH(e, hipLaunchKernelGGL(k_pair_scores<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits));
+  HIPCHK(e, hipGetLastError());
+  return MUAVTA_OK;
+}
+int muavta_pair_scores(MuavtaEnv* e, float* scores, float* logits) {
+  if (!e) return MUAVTA_E_ARG;
+  if (!e->hl.pol_set) { e->err = "muavta_pair_scores: no policy (muavta_set_pair_policy first)"; return MUAVTA_E_STATE; }
+  if (!e->did_reset) { e->err = "muavta_pair_scores before reset"; return MUAVTA_E_STATE; }
+  DeviceScope scope_(e->device);
+  const size_t one = (size_t)e->n_envs * PS_MA * PS_MT * sizeof(float);
+  if (2 * one > e->tok_bytes) {  // (shares the staging buffer of muavta_tokens' host variant)
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->d_tok) hipFree(e->d_tok);
+    e->d_tok = nullptr; e->tok_bytes = 0;
+    HIPCHK(e, hipMalloc(&e->d_tok, 2 * one));
+    e->tok_bytes = 2 * one;
+  }
+  float* ds = (float*)e->d_tok;
+  float* dl = (float*)((char*)e->d_tok + one);
+  if (int rc = muavta_pair_scores_device(e, scores ? ds : nullptr, logits ? dl : nullptr)) return rc;
+  if (scores) HIPCHK(e, hipMemcpyAsync(scores, ds, one, hipMemcpyDeviceToHost, e->stream));
+  if (logits) HIPCHK(e, hipMemcpyAsync(logits, dl, one, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   return MUAVTA_OK;
 }
 

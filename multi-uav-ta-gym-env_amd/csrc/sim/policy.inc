@@ -1,0 +1,165 @@
+// sim/policy.inc — member functions of Sim<TL> (muavta_device.h includes this file INSIDE the struct body): the learned MLP-Pair hybrid.
+  // ====================================================================================================
+  // PairCostHybrid(use_attention=False) (TaskAllocation/Hybrid/PairCostHybrid.py:154-197,266-278,308-328):
+  //   logits = pair_mlp(cat([agent_feats[i], task_feats[j]]))     Linear(25|20, 128) - ReLU - Linear(128, 128) - ReLU - Linear(128, 1)
+  //   scores = tanh(logits) * score_clamp * edge_valid            -> HungarianAllocator.allocate_tasks(edge_scores=...) = allocate<true>
+  // ARITHMETIC CONTRACT (DESIGN.md §7; tests/pair_mlp_py.py is its host twin).  torch leaves its summation order open, so the device
+  // defines its own and keeps to it everywhere:
+  //   * every Linear output is ONE k-ascending float32 fmaf chain that starts from the bias:
+  //         acc = b[n];  for k = 0 .. K-1:  acc = fmaf(W[n][k], x[k], acc)
+  //     layer 1's x is the reference's cat: the agent row's 12 (raw: 11) features, then the task row's 13 (raw: 9) — one chain, not an
+  //     agent part plus a task part; ReLU is `acc > 0 ? acc : 0`; layer 3 runs n-ascending over layer 2's outputs;
+  //   * score = tanhf(logit) * score_clamp, float32, on the pairs whose edge_valid is 1; masked pairs are not evaluated at all.
+  // One PAIR per lane: the lane keeps its pair's 128 hidden activations in registers and walks the chains by itself, the weights are
+  // wave-uniform scalar operands streamed through the scalar cache.  So a logit is a pure function of its 25 (20) inputs and the
+  // weights — the same instruction sequence whatever the lane, the batch, the position in the valid list or the env — and no value
+  // crosses lanes anywhere in the forward pass.  The valid pairs of the 16 x 32 grid are compacted first (row-major), 64 per pass.
+  // ====================================================================================================
+  typedef const __attribute__((address_space(4))) float pol_cf;  // constant address space: uniform indices become scalar loads
+  typedef float pol_f2 __attribute__((ext_vector_type(2)));
+  static DEV float pol_relu(float v) { return v > 0.f ? v : 0.f; }
+  // tf / af / ev: this env's token tensors ([32, Dt], [16, Da], [16, 32]) in global memory, complete and visible (cold_sync() by the
+  // caller).  scores / logits: this env's [16, 32] outputs (either may be null).  fill: masked entries are written as 0 (the fused mode
+  // leaves them alone: allocate<true> under MUAVTA_SC_EDGE_VALID_ONLY never reads them).  Scratch: X.cost .. X.spc (the list of valid cells).
+  template <bool RAW>
+  DEV void pair_forward_t(const PairPolicyDev& pol, const float* tf, const float* af, const float* ev, float* scores, float* logits, bool fill) {
+    constexpr int Da = RAW ? 11 : 12, Dt = RAW ? 9 : 13, K0 = Da + Dt, HID = PW_HID, CELLS = PS_MA * PS_MT;
+    static_assert(K0 <= PW_W0_ROWS && HID % 64 == 0, "layer 1's weights are stored k-major, PW_W0_ROWS rows of HID");
+    // the list of valid cells: the cost tile and the LSAP's duals / spc behind it (one run of doubles, all idle between the token builder and the plan)
+    static_assert(offsetof(Scratch<TL>, resid) - offsetof(Scratch<TL>, cost) >= CELLS * sizeof(uint16_t) && offsetof(Scratch<TL>, u) > offsetof(Scratch<TL>, cost) &&
+                  offsetof(Scratch<TL>, resid) > offsetof(Scratch<TL>, spc), "the list of valid cells needs 1 KB in front of Scratch::resid");
+    const uint64_t wb = (uint64_t)pol.w;
+    uint32_t wlo = __builtin_amdgcn_readfirstlane((uint32_t)wb), whi = __builtin_amdgcn_readfirstlane((uint32_t)(wb >> 32));
+    const float clamp = pol.clamp;
+    uint16_t* list = reinterpret_cast<uint16_t*>(X.cost);
+    int nv = 0;
+    for (int base = 0; base < CELLS; base += WG) {
+      const int c = base + lane;
+      const bool v = ev[c] != 0.f;
+      const unsigned long long m = __ballot(v);
+      if (v) list[nv + prefix_count(m)] = (uint16_t)c;
+      else if (fill) {
+        if (scores) scores[c] = 0.f;
+        if (logits) logits[c] = 0.f;
+      }
+      nv += __popcll(m);
+    }
+    lds_sync();
+    for (int b0 = 0; b0 < nv; b0 += WG) {  // (uniform)
+      // (the weights' base is made opaque once per pass: otherwise layer 1's 128 biases — pass-invariant scalar loads — are hoisted in
+      // front of the loop and held, i.e. spilled, across it)
+      asm volatile("" : "+s"(wlo), "+s"(whi));
+      pol_cf* w = (pol_cf*)(((uint64_t)whi << 32) | (uint64_t)wlo);
+      const bool act = b0 + lane < nv;
+      const int c = list[act ? b0 + lane : b0];  // lanes beyond the list redo the pass's first pair; their result is dropped
+      const int i = c / PS_MT, j = c - i * PS_MT;
+      const float* xa = af + i * Da;
+      const float* xt = tf + j * Dt;
+      // The arithmetic is written two chains wide (v_pk_fma_f32: two independent IEEE fmas per instruction, each chain's own
+      // order untouched): outputs n and n + 1 share an instruction, the input value is broadcast to both halves.
+      // Layer 1, 64 outputs at a time: k is the outer loop, so one pass over the pair's inputs feeds 64 chains that each still take
+      // their products in ascending k.  (Rolled loops with a bounded body on purpose: fully unrolled, every weight of the layer is a
+      // scalar load the scheduler issues up front — thousands of live SGPRs, all spilled.)
+      pol_f2 h1[HID / 2];
+#pragma unroll
+      for (int nc = 0; nc < HID / 2; nc += 32) {
+#pragma unroll
+        for (int t = 0; t < 32; t++) h1[nc + t] = pol_f2{w[PW_B0 + 2 * (nc + t)], w[PW_B0 + 2 * (nc + t) + 1]};
+#pragma unroll 1
+        for (int k = 0; k < K0; k++) {
+          const float xk = *(k < Da ? xa + k : xt + (k - Da));
+          pol_cf* r = w + PW_W0 + k * HID + 2 * nc;
+#pragma unroll
+          for (int t = 0; t < 32; t++) h1[nc + t] = __builtin_elementwise_fma(pol_f2{r[2 * t], r[2 * t + 1]}, pol_f2{xk, xk}, h1[nc + t]);
+        }
+#pragma unroll
+        for (int t = 0; t < 32; t++) h1[nc + t] = pol_f2{pol_relu(h1[nc + t].x), pol_relu(h1[nc + t].y)};
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // Layers 2 and 3 together: four of layer 2's chains side by side (outputs n .. n + 3, their weights interleaved in memory so
+      // that the four of one k are neighbours: PW_W1), eight k at a time, and layer 3's chain takes their outputs in ascending n
+      // as they complete.  The weights of the NEXT eight k are requested right after the first products of a chunk have consumed
+      // the current ones (scalar loads return out of order, so the wait in front of those products must find nothing else in
+      // flight), and arrive while the chunk's other products issue.
+      float logit = w[PW_B2];
+#pragma unroll 1
+      for (int n = 0; n < HID; n += 4) {
+        pol_cf* r = w + PW_W1 + n * HID;  // [k][4]
+        // (no instruction: the activations become new values in every iteration, so the (h, h) operand pairs below are formed where
+        // they are used — as the packed FMA's operand select — instead of once in front of the loop in 128 more register pairs)
+#pragma unroll
+        for (int q = 0; q < HID / 2; q++) asm volatile("" : "+v"(h1[q]));
+        pol_f2 a01 = pol_f2{w[PW_B1 + n], w[PW_B1 + n + 1]}, a23 = pol_f2{w[PW_B1 + n + 2], w[PW_B1 + n + 3]};
+        float cw[32];
+#pragma unroll
+        for (int q = 0; q < 32; q++) cw[q] = r[q];
+#pragma unroll
+        for (int kc = 0; kc < HID; kc += 8) {
+          {
+            const float h = h1[kc / 2].x;
+            a01 = __builtin_elementwise_fma(pol_f2{cw[0], cw[1]}, pol_f2{h, h}, a01);
+            a23 = __builtin_elementwise_fma(pol_f2{cw[2], cw[3]}, pol_f2{h, h}, a23);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          float dw[32];
+          if (kc + 8 < HID) {
+#pragma unroll
+            for (int q = 0; q < 32; q++) dw[q] = r[(kc + 8) * 4 + q];
+          }
+#pragma unroll
+          for (int q = 1; q < 8; q++) {
+            const float h = (q & 1) ? h1[(kc + q) / 2].y : h1[(kc + q) / 2].x;
+            a01 = __builtin_elementwise_fma(pol_f2{cw[4 * q], cw[4 * q + 1]}, pol_f2{h, h}, a01);
+            a23 = __builtin_elementwise_fma(pol_f2{cw[4 * q + 2], cw[4 * q + 3]}, pol_f2{h, h}, a23);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if (kc + 8 < HID) {
+#pragma unroll
+            for (int q = 0; q < 32; q++) cw[q] = dw[q];
+          }
+        }
+        logit = __builtin_fmaf(w[PW_W2 + n], pol_relu(a01.x), logit);
+        logit = __builtin_fmaf(w[PW_W2 + n + 1], pol_relu(a01.y), logit);
+        logit = __builtin_fmaf(w[PW_W2 + n + 2], pol_relu(a23.x), logit);
+        logit = __builtin_fmaf(w[PW_W2 + n + 3], pol_relu(a23.y), logit);
+      }
+      if (act) {
+        if (logits) logits[c] = logit;
+        if (scores) scores[c] = tanhf(logit) * clamp;
+      }
+    }
+    lds_sync();
+  }
+  DEV void pair_forward(const PairPolicyDev& pol, const float* tf, const float* af, const float* ev, float* scores, float* logits, bool fill) {
+    if (pol.raw) pair_forward_t<true>(pol, tf, af, ev, scores, logits, fill);  // (uniform)
+    else pair_forward_t<false>(pol, tf, af, ev, scores, logits, fill);
+  }
+  // build_pair_tokens(env, 32, 16[, raw]) of the current state into this env's scratch block
+  DEV void pair_tokens_scratch(const PairPolicyDev& pol, float* base) {
+    TokPtrs K;
+    K.task_feats = base + PS_TF; K.agent_feats = base + PS_AF; K.edge_valid = base + PS_EV;
+    K.task_ids = reinterpret_cast<int32_t*>(base + PS_TID); K.agent_ids = reinterpret_cast<int32_t*>(base + PS_AID);
+    K.task_mask = reinterpret_cast<uint8_t*>(base + PS_TMASK); K.agent_mask = reinterpret_cast<uint8_t*>(base + PS_AMASK);
+    K.n_urgent = nullptr; K.expert_mask = nullptr; K.replanned = nullptr;
+    K.kind = pol.raw ? 1 : 0; K.max_tasks = PS_MT; K.max_agents = PS_MA;
+    cold_sync();  // the token rows read currentReqs / allocatedReqs
+    tokens(K, 0);
+    cold_sync();  // every lane's rows are in memory before any lane reads another's
+  }
+  // MUAVTA_ALLOC_MLP_PAIR: what wps_eval's loop does at a step with policy = PairCostHybrid(use_attention=False) (experiments/
+  // wps_eval.py:244-254,490-492; train_pair_cost.py:73-93 with its own interval) —
+  //     if _should_replan(env, events, interval):  tok = build_tokens(env); scores = score_tokens(tok); result = plan(.., scores=scores)
+  // — tokens and scores only where the gate fires (uniform), then the scored Hungarian with the gate, the token pads and the flags the
+  // reference's plan uses.  scratch: this env's PS_FLOATS block; sc_list: T bytes of LDS behind the tile (allocate<true>'s task list).
+  DEV void allocate_mlp(int interval, int use_visibility, const PairPolicyDev& pol, float* scratch, uint8_t* sc_list) {
+    if (gate_fires(MUAVTA_GATE_TRAINER, interval)) {
+      pair_tokens_scratch(pol, scratch);
+      pair_forward(pol, scratch + PS_TF, scratch + PS_AF, scratch + PS_EV, scratch + PS_SCORES, nullptr, false);
+      cold_sync();  // the scores are in memory before the cost evaluation reads them across lanes
+    }
+    ScoredDev sc;
+    sc.scores = scratch + PS_SCORES; sc.pri = nullptr; sc.reserved = nullptr; sc.selected = nullptr; sc.replanned = nullptr;
+    sc.kind = pol.raw ? 1 : 0; sc.MT = PS_MT; sc.MA = PS_MA; sc.gate = MUAVTA_GATE_TRAINER; sc.flags = MUAVTA_SC_EDGE_VALID_ONLY;
+    allocate<true>(interval, use_visibility, 4, &sc, 0, sc_list);
+  }
+

@@ -35,6 +35,7 @@ EXPORTS = [
     "muavta_step_part", "muavta_observe_part", "muavta_wait_part", "muavta_domain_math", "muavta_domain_log", "muavta_domain_atan2", "muavta_step_lists",
     "muavta_allocate_scored", "muavta_allocate_scored_device", "muavta_rl_step_device", "muavta_launch_gaps_ms",
     "muavta_rl_run_device", "muavta_step_run", "muavta_set_lanes", "muavta_lanes", "muavta_rollout_metrics_back", "muavta_error_flags_back", "muavta_set_slot_cap", "muavta_context", "muavta_context_device",
+    "muavta_set_pair_policy", "muavta_pair_scores", "muavta_pair_scores_device",
 ]
 
 
@@ -48,6 +49,12 @@ class MuavtaScored(C.Structure):
                 ("replan_interval", C.c_int32), ("use_visibility", C.c_int32), ("reserved0", C.c_int32),
                 ("edge_scores", C.c_void_p), ("task_pri", C.c_void_p), ("reserved", C.c_void_p), ("selected", C.c_void_p),
                 ("replanned", C.c_void_p)]
+
+
+class MuavtaPairMlp(C.Structure):
+    """include/muavta.h: MuavtaPairMlp (muavta_set_pair_policy)."""
+    _fields_ = [("raw_features", C.c_int32), ("hidden", C.c_int32), ("score_clamp", C.c_float)] + [
+        (n, C.c_void_p) for n in ("w0", "b0", "w1", "b1", "w2", "b2")]
 
 
 def sources():
@@ -180,6 +187,9 @@ def lib() -> C.CDLL:
     L.muavta_set_slot_cap.argtypes = [vp, i32]
     L.muavta_context.argtypes = [vp, i32, i32, vp]
     L.muavta_context_device.argtypes = [vp, i32, i32, vp]
+    L.muavta_set_pair_policy.argtypes = [vp, C.POINTER(MuavtaPairMlp)]
+    L.muavta_pair_scores.argtypes = [vp, vp, vp]
+    L.muavta_pair_scores_device.argtypes = [vp, vp, vp]
     L.muavta_lanes.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.muavta_rollout_metrics_back.argtypes = [vp, i32, vp]
     L.muavta_error_flags_back.argtypes = [vp, i32, vp]

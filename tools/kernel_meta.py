@@ -10,8 +10,9 @@ import tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-# names of the bool template arguments behind the tile (k_rollout<TL, REC, BL>, k_allocate<TL, BL>; BL = the baseline allocators)
-FLAGS = {"k_rollout": ("REC", "BL"), "k_allocate": ("BL",)}
+# names of the bool template arguments behind the tile (k_rollout<TL, REC, BL, PM>, k_allocate<TL, BL, PM>; BL = the baseline allocators,
+# PM = the learned MLP-Pair hybrid)
+FLAGS = {"k_rollout": ("REC", "BL", "PM"), "k_allocate": ("BL", "PM")}
 
 
 def short(name):
