@@ -1617,6 +1617,9 @@ int muavta_create(const MuavtaParams* params, int32_t n_envs, int32_t device, Mu
   CK(hipMalloc(&e->cold, N * e->cold_bytes));
   CK(hipMemsetAsync(e->cold, 0, N * e->cold_bytes, e->stream));
   CK(hipMalloc(&e->tapes, N * MUAVTA_RNG_STREAMS * MUAVTA_RNG_WORDS * sizeof(uint32_t)));
+  // zeroed like the blobs: without obstacles the obs stream is never seeded, yet every step prefetches its next eight words into
+  // rng_win — whatever the allocation held would end up in get_state / get_rng, different from one handle to the next
+  CK(hipMemsetAsync(e->tapes, 0, N * MUAVTA_RNG_STREAMS * MUAVTA_RNG_WORDS * sizeof(uint32_t), e->stream));
   for (int b = 0; b < 2; b++) {
     CK(hipMalloc(&e->d_seeds[b], N * sizeof(uint64_t)));
     CK(hipHostMalloc((void**)&e->h_seeds[b], N * sizeof(uint64_t), hipHostMallocDefault));

@@ -1963,6 +1963,11 @@ int orc_rollout(void* h, uint64_t seed, int do_reset, int n_steps, int interval,
   return s;
 }
 void orc_metrics(void* h, double* out) { ((Env*)h)->metrics(out); }
+// MT19937 words drawn since reset(), per stream (agent, obs, tgt, mission): words // 624 is the block a stream's cursor is in
+void orc_rng_words(void* h, uint64_t out[4]) {
+  Env* e = (Env*)h;
+  out[0] = e->rndAgent.words_drawn; out[1] = e->rndObs.words_drawn; out[2] = e->rndTgt.words_drawn; out[3] = e->rndMission.words_drawn;
+}
 int orc_lsap(const double* cost, int nr, int nc, int64_t* row, int64_t* col) { return lsap_solve(cost, nr, nc, row, col); }
 
 void orc_dims(void* h, int32_t* out) {

@@ -148,6 +148,12 @@ class OracleEnv:
         self.L.orc_metrics(self.h, _p(m))
         return m
 
+    def rng_words(self):
+        """MT19937 words drawn since reset(), per stream (agent, obs, tgt, mission)."""
+        w = np.zeros(4, dtype=np.uint64)
+        self.L.orc_rng_words(self.h, _p(w))
+        return [int(x) for x in w]
+
     def agents(self):
         rows = np.zeros((self.A, 16)); caps = np.zeros((self.A, 6)); q = np.zeros((self.A, self.QCAP), dtype=np.int32)
         self.L.orc_get_agents(self.h, _p(rows), _p(caps), _p(q), self.QCAP)
@@ -260,11 +266,12 @@ def lsap(cost):
 # ---------------------------------------------------------------------------------------------------------------
 # Oracle episodes in parallel worker processes (spawned, so they never inherit a GPU context): the checker for the
 # full-size GPU tests.  Returns the [len(seeds), 30] metrics array of `rollout_mode(seed, 150, interval, use_vis, mode)`.
+# `case`: a registry case name, or a MuavtaParams (it travels to the workers as its bytes).
 def _metrics_worker(args):
     case, seeds, n_steps, interval, use_vis, mode = args
     import numpy as _np
-    from muavta_amd.params import params_for_case
-    e = OracleEnv(params_for_case(case))
+    from muavta_amd.params import MuavtaParams, params_for_case
+    e = OracleEnv(params_for_case(case) if isinstance(case, str) else MuavtaParams.from_buffer_copy(case))
     out = _np.zeros((len(seeds), 30))
     for i, s in enumerate(seeds):
         e.rollout_mode(int(s), n_steps, interval, use_vis, mode)
@@ -276,6 +283,8 @@ def parallel_metrics(case, seeds, interval, use_vis=1, mode=0, n_steps=150, proc
     import multiprocessing as mp
     lib()  # build the oracle once, before the workers race for it
     seeds = [int(s) for s in seeds]
+    if not isinstance(case, str):
+        case = bytes(case)
     try:
         cores = len(os.sched_getaffinity(0))
     except AttributeError:
