@@ -955,2020 +955,10 @@ __global__ void k_avoid(const double* pos, const double* mov, int n, const doubl
 // ====================================================================================================
 // Host side
 // ====================================================================================================
-thread_local std::string g_create_error;
-
-#define HIPCHK(env, expr)                                                                         \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) {                                                                       \
-      (env)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                             \
-      return MUAVTA_E_HIP;                                                                        \
-    }                                                                                             \
-  } while (0)
-
-enum TileKind { TK16 = 0, TK24 = 1, TK64 = 2 };
-
-// An ABI call runs on its handle's device and leaves the calling thread's current device as it found it (a caller that
-// mixes this library with torch on another device must not have its current device changed under it).
-struct DeviceScope {
-  int prev = -1, want;
-  explicit DeviceScope(int d) : want(d) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != want) (void)hipSetDevice(want);
-  }
-  ~DeviceScope() { if (prev >= 0 && prev != want) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
-struct MuavtaEnv {
-  DevParams P;
-  MuavtaParams params;
-  int tile = TK16;
-  int alloc_mode = 0;  // MUAVTA_ALLOC_*
-  void* d_tok = nullptr;  // muavta_tokens staging (host-buffer variant)
-  double* d_rel = nullptr;  // release log [N, 1 + MUAVTA_REL_ROW*T] (muavta_set_release_log)
-  // Seeding pipeline: seeds upload + k_seed run on their own stream into one of two slots, so that the seeding of launch
-  // i+1 overlaps launch i (k_seed uses no LDS and few registers: its waves run next to the rollout's where a SIMD has room).
-  uint32_t* d_seedbuf[2] = {nullptr, nullptr};  // [N][4][624] init_by_array states (k_seed)
-  uint32_t* d_seedtmp = nullptr;                // k_seed's lane-interleaved scratch
-  uint64_t* h_seeds[2] = {nullptr, nullptr};    // pinned staging of the caller's seeds
-  hipStream_t seed_stream = nullptr;
-  hipEvent_t ev_seed0[2] = {nullptr, nullptr}, ev_seeded[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr};
-  bool seed_used[2] = {false, false};
-  unsigned seed_seq = 0;
-  int last_seed_slot = 0;
-  size_t tok_bytes = 0;
-  int n_envs = 0, device = 0;
-  int A = 0, T = 0, H = 0, E = 0, R = 0, Q = 0;
-  size_t state_bytes = 0, cold_bytes = 0, lds_bytes = 0;  // per env: LDS image (EnvState), HBM-only part (EnvCold)
-  void* blobs = nullptr;
-  void* cold = nullptr;
-  uint32_t* tapes = nullptr;
-  DevCtx* d_ctx = nullptr;  // device copy of {P, O, tapes}
-  uint32_t* d_pace = nullptr;
-  uint32_t pace_epoch = 0;
-  enum { REC_SLOT = 256 };
-  void* d_rec = nullptr;  // [2][REC_SLOT]: slot 0 all zero (plain rollouts), slot 1 the RecordPtrs of the muavta_rollout_record launch in flight
-  uint64_t* d_seeds[2] = {nullptr, nullptr};
-  int32_t *d_act_agent = nullptr, *d_act_index = nullptr, *d_call_out = nullptr;
-  int32_t *d_list_agent = nullptr, *d_list_index = nullptr;  // muavta_step_lists rows [N][list_cap] (grown on demand)
-  void* d_run = nullptr;  // muavta_step_run's outputs: [N] f64 reward sums | [N] i32 steps taken | [N] u8 park flags
-  int list_cap = 0;
-  ncclComm_t comm = nullptr;  // muavta_comm_init
-  int comm_rank = 0, comm_ranks = 0;
-  void* d_comm = nullptr;     // [64 f64 send | 64 x n_ranks f64 recv | 64 i64 send | 64 i64 recv]
-  double* d_metrics = nullptr;
-  float *d_pol_w = nullptr, *d_pol_scratch = nullptr;  // muavta_set_pair_policy: this lane's copy of the packed weights, its per-env token / score scratch
-  ObsPtrs O{};
-  hipStream_t stream = nullptr;
-  // sub-batches (muavta_set_parts): contiguous env ranges, each stepped on its own stream so that the host can decide for one part
-  // while the device steps another, and so that one part's slowest env does not hold up the others' launches
-  enum { MAX_PARTS = 8 };
-  int n_parts = 0;
-  hipStream_t part_stream[MAX_PARTS] = {};
-  hipEvent_t part_ev[MAX_PARTS] = {};
-  hipEvent_t ev_fork = nullptr;
-  bool part_busy[MAX_PARTS] = {};         // the part's stream holds work the main stream has not been ordered after yet
-  bool part_fork_needed[MAX_PARTS] = {};  // the main stream got work since the part's stream last waited for it
-  int32_t *d_part_agent = nullptr, *d_part_index = nullptr;  // action staging of the parts (one [N, A] pair, each part its rows)
-  enum { EV_RING = 64 };
-  hipEvent_t ev0[EV_RING] = {}, ev1[EV_RING] = {};  // ev0[i] .. ev1[i]: the k_rollout launch number i (mod EV_RING)
-  unsigned long long n_rollouts = 0;
-  bool timing_stale = false;  // a *_part rollout ran since the last whole-batch one: the event ring describes an older launch
-  float last_ms = 0.f;
-  bool last_seeded = false;
-  bool did_reset = false;
-  std::vector<unsigned char> host_blobs, host_cold;  // cache for muavta_get
-  bool host_valid = false;
-  std::string err;
-  // ---- state lanes (muavta_set_lanes) -----------------------------------------------------------------------------------------------
-  // Everything above is ONE lane: the env records, tapes, observation buffers, metrics, streams, seeding slots and event rings of a batch.
-  // A handle may own a second one (`hl.twin`, a complete MuavtaEnv of the same configuration that no caller ever sees): a seeded rollout
-  // issued while the previous one is still running goes to the other lane — launch i + 1's workgroups start in the wave slots launch i's
-  // early finishers free instead of waiting for its slowest env.  A flip SWAPS the two objects' contents (everything but `hl` and the
-  // communicator), so every entry point keeps working on `*e` = the lane of the latest seeded rollout, without routing.
-  int lane_id = 0;  // travels with the lane's contents
-  struct HandleLevel {
-    MuavtaEnv* twin = nullptr;
-    int lanes_mode = 0;  // 0 auto (second lane on demand), 1 one lane only, 2 always alternate
-    bool twin_failed = false;
-    enum { RING = 64 };
-    unsigned char ring_lane[RING] = {};         // rollout launch k (mod RING) of the HANDLE ran on this lane ...
-    unsigned long long ring_no[RING] = {};      // ... as that lane's launch number
-    unsigned long long n_launches = 0;
-    std::vector<hipEvent_t> pending_waits;  // muavta_wait_stream events recorded while there was no second lane: one created later waits on them
-    // muavta_set_pair_policy: the packed weights (PW_* layout) as the caller last set them — a second lane created later gets its copy from here
-    std::vector<float> pol_w;
-    int pol_raw = 0;
-    float pol_clamp = 0.f;
-    bool pol_set = false;
-  } hl;
-};
-static int join_parts(MuavtaEnv* e);  // (sub-batches: defined with the other part helpers in front of the C ABI)
-extern "C" int muavta_set_parts(MuavtaEnv* e, int32_t n_parts);
-extern "C" int muavta_set_release_log(MuavtaEnv* e, int32_t enable);
-extern "C" int muavta_create(const MuavtaParams* params, int32_t n_envs, int32_t device, MuavtaEnv** out);
-extern "C" int muavta_destroy(MuavtaEnv* e);
-extern "C" int muavta_set_slot_cap(MuavtaEnv* e, int32_t cap);
-static int push_policy(MuavtaEnv* lane, const MuavtaEnv::HandleLevel& hl);
-
-namespace {
-
-template <class TL>
-int launch_attr(MuavtaEnv* e) {
-  size_t lds = Lds<TL>::bytes();
-  e->lds_bytes = lds;
-  if (lds > 48 * 1024) {
-    const void* ks[] = {reinterpret_cast<const void*>(&k_reset<TL>), reinterpret_cast<const void*>(&k_step<TL>), reinterpret_cast<const void*>(&k_allocate<TL>),
-                        reinterpret_cast<const void*>(&k_rollout<TL, false>), reinterpret_cast<const void*>(&k_rollout<TL, true>), reinterpret_cast<const void*>(&k_metrics<TL>), reinterpret_cast<const void*>(&k_observe<TL>),
-                        reinterpret_cast<const void*>(&k_tokens<TL>), reinterpret_cast<const void*>(&k_call<TL>), reinterpret_cast<const void*>(&k_context<TL>),
-                        reinterpret_cast<const void*>(&k_allocate<TL, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, true>),
-                        reinterpret_cast<const void*>(&k_pair_scores<TL>), reinterpret_cast<const void*>(&k_rollout<TL, false, false, true>)};
-    for (const void* k : ks) HIPCHK(e, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate<TL, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate_scored<TL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
-  }
-  return MUAVTA_OK;
-}
-
-#define DISPATCH(e, CALL)                    \
-  switch ((e)->tile) {                       \
-    case TK16: { typedef Tile16 TL; CALL; } break; \
-    case TK24: { typedef Tile24 TL; CALL; } break; \
-    default:   { typedef Tile64 TL; CALL; } break; \
-  }
-
-template <class TL>
-static void launch_tokens(MuavtaEnv* e, int kind, int max_tasks, int max_agents, float* task_feats, uint8_t* task_mask, int32_t* task_ids,
-                          float* agent_feats, uint8_t* agent_mask, int32_t* agent_ids, float* edge_valid, int32_t* n_urgent, float* expert_mask,
-                          int32_t* replanned) {
-  typename Sim<TL>::TokPtrs K{task_feats, task_mask, task_ids, agent_feats, agent_mask, agent_ids, edge_valid, n_urgent, expert_mask, replanned,
-                              kind, max_tasks, max_agents};
-  hipLaunchKernelGGL(k_tokens<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, K);
-}
-
-template <class TL>
-static void launch_rl_step(MuavtaEnv* e, const ScoredDev& sc, const MuavtaRlStep* rs, hipStream_t stream, int first, int count) {
-  typename Sim<TL>::TokPtrs K{rs->task_feats, rs->task_mask, rs->task_ids, rs->agent_feats, rs->agent_mask, rs->agent_ids, rs->edge_valid, rs->n_urgent,
-                              nullptr, nullptr, rs->plan.kind, rs->plan.max_tasks, rs->plan.max_agents};
-  hipLaunchKernelGGL(k_rl_step<TL>, dim3(count), dim3(WG), 0, stream, (const DevCtx*)e->d_ctx, sc, K, rs->plan.replan_interval, rs->plan.use_visibility,
-                     rs->write_obs, rs->s_wps, rs->done, e->n_envs, first);
-}
-
-template <class TL>
-static void launch_run(MuavtaEnv* e, int src, const ScoredDev& sc, const MuavtaRlStep* rs, const MuavtaRlRun* rr, const RunOut& R, int gate, int interval, int use_vis,
-                       int write_obs, int max_steps, const int32_t* da, const int32_t* di, int cap, hipStream_t stream, int first, int count) {
-  RunArgs<TL> G;
-  memset(&G, 0, sizeof(G));
-  G.sc = sc; G.R = R;
-  if (rs) {
-    typename Sim<TL>::TokPtrs k{rs->task_feats, rs->task_mask, rs->task_ids, rs->agent_feats, rs->agent_mask, rs->agent_ids, rs->edge_valid, rs->n_urgent,
-                                nullptr, nullptr, rs->plan.kind, rs->plan.max_tasks, rs->plan.max_agents};
-    G.K = k;
-  }
-  if (rr && rs) {
-    typename Sim<TL>::TokPtrs k{rr->park_task_feats, rr->park_task_mask, rr->park_task_ids, rr->park_agent_feats, rr->park_agent_mask, rr->park_agent_ids, rr->park_edge_valid,
-                                rr->park_n_urgent, nullptr, nullptr, rs->plan.kind, rs->plan.max_tasks, rs->plan.max_agents};
-    G.KP = k;
-  }
-  hipLaunchKernelGGL(k_run<TL>, dim3(count), dim3(WG), 0, stream, G, (const DevCtx*)e->d_ctx, src, gate, interval, use_vis, write_obs, max_steps, da, di, cap, e->n_envs, first);
-}
-
-int fill_dev_params(const MuavtaParams* p, DevParams* d, std::string* err) {
-  memset(d, 0, sizeof(*d));
-  if (p->abi_version != MUAVTA_ABI_VERSION) { *err = "abi_version mismatch"; return MUAVTA_E_ARG; }
-  if (p->n_agent_groups < 1 || p->n_agent_groups > MUAVTA_MAX_GROUPS || p->n_task_groups < 0 || p->n_task_groups > MUAVTA_MAX_GROUPS ||
-      p->n_threat_groups < 0 || p->n_threat_groups > MUAVTA_MAX_GROUPS) { *err = "group counts out of range"; return MUAVTA_E_ARG; }
-  d->n_agent_groups = p->n_agent_groups; d->n_task_groups = p->n_task_groups; d->n_threat_groups = p->n_threat_groups;
-  int nA = 0, nT = 0, nH = 0;
-  double possible = 0;  // DroneEnv.py:670-675: summed over the static tasks only (Det tasks are created later, :685)
-  for (int g = 0; g < p->n_agent_groups; g++) {
-    if (p->agent_type[g] < 0 || p->agent_type[g] > MUAVTA_F2 || p->agent_count[g] < 0) { *err = "bad agent group"; return MUAVTA_E_ARG; }
-    d->agent_type[g] = p->agent_type[g]; d->agent_count[g] = p->agent_count[g]; nA += p->agent_count[g];
-  }
-  for (int g = 0; g < p->n_task_groups; g++) {
-    int ty = p->task_type[g];
-    if (ty != MUAVTA_HOLD && ty != MUAVTA_REC && ty != MUAVTA_ATT) { *err = "static task types are Hold/Rec/Att"; return MUAVTA_E_ARG; }
-    d->task_type[g] = ty; d->task_count[g] = p->task_count[g]; nT += p->task_count[g];
-    for (int i = 0; i < p->task_count[g]; i++) possible += 1.0;
-  }
-  for (int g = 0; g < p->n_threat_groups; g++) {
-    int ty = p->threat_type[g];
-    if (ty != MUAVTA_T1 && ty != MUAVTA_T2) { *err = "threat types are T1/T2"; return MUAVTA_E_ARG; }
-    d->threat_type[g] = ty; d->threat_count[g] = p->threat_count[g]; nH += p->threat_count[g];
-  }
-  if (nA < 1) { *err = "no agents"; return MUAVTA_E_ARG; }
-  if (p->num_obstacles < 0 || p->num_obstacles > 8) { *err = "num_obstacles must be in 0..8"; return MUAVTA_E_ARG; }
-  if (p->max_time_steps < 1) { *err = "max_time_steps must be >= 1"; return MUAVTA_E_ARG; }
-  // (agent speeds = MAX_SPEED / frame_rate * 0.02 are divisors of the kernels' range-restricted division, see fdiv)
-  if (!(p->simulation_frame_rate >= 1e-9 && p->simulation_frame_rate <= 1e9)) { *err = "simulation_frame_rate must be in [1e-9, 1e9]"; return MUAVTA_E_ARG; }
-  // time steps, deadlines (t + window_length), reveal times (t + threat_delay), commit locks (t + commit_horizon) and task
-  // ids (a few per step) are stored in 16 bits on the device
-  if (p->max_time_steps > 20000 || p->window_length > 10000 || p->threat_delay > 10000 || p->commit_horizon > 10000 || p->window_length < -10000 ||
-      p->threat_delay < -10000 || p->commit_horizon < -10000) { *err = "max_time_steps <= 20000 and window_length / threat_delay / commit_horizon within +-10000"; return MUAVTA_E_ARG; }
-  d->n_agents = nA; d->n_tasks = nT + 1; d->max_tasks = d->n_tasks + 28; d->n_threats = nH;
-  d->max_time_steps = p->max_time_steps; d->multiple_tasks_per_agent = p->multiple_tasks_per_agent;
-  d->early_terminate = p->early_terminate; d->capability_mask = p->capability_mask; d->saturate_mask = p->saturate_mask;
-  d->include_time_windows = p->include_time_windows; d->threat_delay = p->threat_delay; d->hard_windows = p->hard_windows;
-  d->window_length = p->window_length; d->burst_mode = p->burst_mode; d->burst_size = p->burst_size;
-  d->dual_region_bursts = p->dual_region_bursts; d->share_knowledge = p->share_knowledge; d->escort_enabled = p->escort_enabled;
-  d->num_obstacles = p->num_obstacles; d->random_init_pos = p->random_init_pos;
-  int need = (int)std::ceil(p->escort_requirement);
-  d->escort_required_agents = need > 2 ? need : 2;
-  d->escort_mask = p->escort_agent_type_mask;
-  d->commit_horizon = p->commit_horizon;
-  static const double MAX_SPEED[7] = {5.0, 8.0, 5.0, 20.0, 15.0, 14.0, 12.0};  // MultiDroneEnvData.py:32-38
-  for (int t = 0; t < 7; t++) d->speed[t] = MAX_SPEED[t] / p->simulation_frame_rate * 0.02;
-  d->threat_prob = 0.7 / p->simulation_frame_rate * 0.02;
-  d->reward_norm_factor = (possible * 1 + possible) / 1000;
-  // sqrt is correctly rounded and monotone, so `sqrt(v) <= r` is a threshold test on v; find the threshold
-  auto sq_bound = [](double r) {
-    double v = r * r;
-    if (r > 0) {
-      while (std::sqrt(v) > r) v = std::nextafter(v, 0.0);
-      while (std::sqrt(std::nextafter(v, INFINITY)) <= r) v = std::nextafter(v, INFINITY);
-    }
-    return v;
-  };
-  d->sense_sq_bound = sq_bound(p->sense_radius);
-  d->escort_sq_bound = sq_bound(p->escort_radius);
-  d->fail_rate = p->fail_rate; d->arrival_rate = p->arrival_rate; d->dynamic_idle_penalty = p->dynamic_idle_penalty;
-  d->sense_radius = p->sense_radius; d->miss_penalty = p->miss_penalty; d->on_time_bonus = p->on_time_bonus;
-  d->reassign_penalty = p->reassign_penalty; d->escort_radius = p->escort_radius; d->escort_requirement = p->escort_requirement;
-  d->escort_intercept_radius = p->escort_intercept_radius; d->mutual_support_radius = p->mutual_support_radius;
-  for (int i = 0; i < 8; i++) d->rw[i] = p->reward_weights[i];
-  d->rw_plain = d->reward_norm_factor > 0 ? 1 : 0;
-  for (int i = 0; i < 8; i++) if (!(p->reward_weights[i] >= 0 && std::isfinite(p->reward_weights[i]))) d->rw_plain = 0;
-  d->inv_mts = 1.0 / (double)(d->max_time_steps > 1 ? d->max_time_steps : 1);
-  d->inv_max_tasks = 1.0 / (double)(d->max_tasks > 1 ? d->max_tasks : 1);
-  return MUAVTA_OK;
-}
-
-template <class TL>
-size_t blob_bytes() { return sizeof(EnvState<TL>); }
-
-int sync_host(MuavtaEnv* e) {
-  if (e->host_valid) return MUAVTA_OK;
-  if (e->n_parts) { int rc_ = join_parts(e); if (rc_) return rc_; }
-  e->host_blobs.resize((size_t)e->n_envs * e->state_bytes);
-  e->host_cold.resize((size_t)e->n_envs * e->cold_bytes);
-  HIPCHK(e, hipMemcpyAsync(e->host_blobs.data(), e->blobs, e->host_blobs.size(), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipMemcpyAsync(e->host_cold.data(), e->cold, e->host_cold.size(), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  e->host_valid = true;
-  return MUAVTA_OK;
-}
-
-// Gather one field out of the host copy of the blobs.
-template <class TL>
-int gather(MuavtaEnv* e, MuavtaField f, void* dst, size_t bytes, bool scatter) {
-  typedef EnvState<TL> St;
-  const int N = e->n_envs, A = e->P.n_agents, T = TL::T, H = e->P.n_threats, Q = TL::Q, E = TL::E, KW = TL::KW;
-  St* blobs = reinterpret_cast<St*>(e->host_blobs.data());
-  EnvCold<TL>* cold = reinterpret_cast<EnvCold<TL>*>(e->host_cold.data());
-  size_t need = 0;
-  auto chk = [&](size_t n) { need = n; return bytes == n; };
-  double* D = (double*)dst;
-  int32_t* I = (int32_t*)dst;
-  uint32_t* U = (uint32_t*)dst;
-  auto QS = [&](int n) -> QueueSide<TL::A, TL::T, true>& {  // where this tile keeps next_free_* / orgReqs / doneReqs
-    if constexpr (TL::SLIM) return static_cast<QueueSide<TL::A, TL::T, true>&>(cold[n]); else return static_cast<QueueSide<TL::A, TL::T, true>&>(blobs[n]);
-  };
-#define BAD() do { e->err = "muavta_get/set: buffer size mismatch, need " + std::to_string(need) + " bytes"; return MUAVTA_E_ARG; } while (0)
-#define RW(dstv, srcv) do { if (scatter) (srcv) = (dstv); else (dstv) = (srcv); } while (0)
-  switch (f) {
-    case MUAVTA_F_AGENT_POS:
-      if (!chk((size_t)N * A * 2 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) { RW(D[((size_t)n * A + a) * 2], blobs[n].a_px[a]); RW(D[((size_t)n * A + a) * 2 + 1], blobs[n].a_py[a]); }
-      break;
-    case MUAVTA_F_AGENT_NFP:
-      if (!chk((size_t)N * A * 2 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) { RW(D[((size_t)n * A + a) * 2], QS(n).a_nfx[a]); RW(D[((size_t)n * A + a) * 2 + 1], QS(n).a_nfy[a]); }
-      break;
-    case MUAVTA_F_AGENT_NFT:
-      if (!chk((size_t)N * A * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) RW(D[(size_t)n * A + a], QS(n).a_nft[a]);
-      break;
-    case MUAVTA_F_AGENT_DIST:
-      if (!chk((size_t)N * A * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) RW(D[(size_t)n * A + a], blobs[n].a_dist[a]);
-      break;
-    case MUAVTA_F_AGENT_CAPS:
-      if (!chk((size_t)N * A * 6 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) for (int c = 0; c < 6; c++) RW(D[((size_t)n * A + a) * 6 + c], blobs[n].a_caps[c][a]);
-      break;
-    case MUAVTA_F_AGENT_STATE:
-      if (!chk((size_t)N * A * 4)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) RW(I[(size_t)n * A + a], blobs[n].a_state[a]);
-      break;
-    case MUAVTA_F_AGENT_HEAD:
-      if (!chk((size_t)N * A * 4)) BAD();
-      if (scatter) { e->err = "AGENT_HEAD is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) I[(size_t)n * A + a] = blobs[n].a_qlen[a] > 0 ? blobs[n].a_qid[a][0] : 0;
-      break;
-    case MUAVTA_F_AGENT_QUEUE:
-      if (!chk((size_t)N * A * Q * 4)) BAD();
-      if (scatter) { e->err = "AGENT_QUEUE is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) for (int k = 0; k < Q; k++)
-        I[((size_t)n * A + a) * Q + k] = k < blobs[n].a_qlen[a] ? blobs[n].a_qid[a][k] : (k == 0 ? 0 : -1);
-      break;
-    case MUAVTA_F_AGENT_ATTACK_CAP:
-      if (!chk((size_t)N * A * 4)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) RW(I[(size_t)n * A + a], blobs[n].a_acap[a]);
-      break;
-    case MUAVTA_F_AGENT_TYPE:
-      if (!chk((size_t)N * A * 4)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) RW(I[(size_t)n * A + a], blobs[n].a_type[a]);
-      break;
-    case MUAVTA_F_AGENT_NAME_IDX:
-      if (!chk((size_t)N * A * 4)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) RW(I[(size_t)n * A + a], blobs[n].a_name[a]);
-      break;
-    case MUAVTA_F_AGENT_MISC:
-      if (!chk((size_t)N * A * 6 * 4)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) {
-        int32_t* r = I + ((size_t)n * A + a) * 6;
-        RW(r[0], blobs[n].a_task_start[a]); RW(r[1], blobs[n].a_fail[a]); RW(r[2], blobs[n].a_reeval[a]);
-        RW(r[3], blobs[n].a_last_id[a]); RW(r[4], blobs[n].a_commit[a]);
-        if (!scatter) r[5] = blobs[n].a_qlen[a];
-      }
-      break;
-    case MUAVTA_F_TASK_ID:
-      if (!chk((size_t)N * T * 4)) BAD();
-      if (scatter) { e->err = "TASK_ID is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) I[(size_t)n * T + s] = blobs[n].t_id[s];
-      break;
-    case MUAVTA_F_TASK_STATUS:
-      if (!chk((size_t)N * T * 4)) BAD();
-      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) RW(I[(size_t)n * T + s], blobs[n].t_status[s]);
-      break;
-    case MUAVTA_F_TASK_POS:
-      if (!chk((size_t)N * T * 2 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) { RW(D[((size_t)n * T + s) * 2], blobs[n].t_px[s]); RW(D[((size_t)n * T + s) * 2 + 1], blobs[n].t_py[s]); }
-      break;
-    case MUAVTA_F_TASK_CUR:
-      if (!chk((size_t)N * T * 6 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) for (int c = 0; c < 6; c++) RW(D[((size_t)n * T + s) * 6 + c], cold[n].t_cur[c][s]);
-      break;
-    case MUAVTA_F_TASK_ALLOC:
-      if (!chk((size_t)N * T * 6 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) for (int c = 0; c < 6; c++) RW(D[((size_t)n * T + s) * 6 + c], cold[n].t_alloc[c][s]);
-      break;
-    case MUAVTA_F_TASK_ORG_DONE:
-      if (!chk((size_t)N * T * 2 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) { RW(D[((size_t)n * T + s) * 2], QS(n).t_org[s]); RW(D[((size_t)n * T + s) * 2 + 1], QS(n).t_done[s]); }
-      break;
-    case MUAVTA_F_TASK_TIMES:
-      if (!chk((size_t)N * T * 2 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) { RW(D[((size_t)n * T + s) * 2], cold[n].t_init[s]); RW(D[((size_t)n * T + s) * 2 + 1], cold[n].t_dtime[s]); }
-      break;
-    case MUAVTA_F_TASK_META:
-      if (!chk((size_t)N * T * 8 * 4)) BAD();
-      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) {
-        int32_t* r = I + ((size_t)n * T + s) * 8;
-        St& b = blobs[n];
-        if (scatter) { b.t_required[s] = r[3]; continue; }  // required_agents is the only field callers write (test_escort.py:107)
-        r[0] = b.t_type[s]; r[1] = (b.t_flags[s] & TF_DEADLINE) ? b.t_deadline[s] : -1; r[2] = b.t_created[s]; r[3] = b.t_required[s];
-        r[4] = (b.t_flags[s] & TF_ESCORT) ? 1 : 0; r[5] = b.t_ndet[s]; r[6] = b.t_prot_agent[s];
-        r[7] = (b.t_flags[s] & TF_ELIGIBLE) ? (int32_t)b.t_elig[s] : -1;
-      }
-      break;
-    case MUAVTA_F_KNOWN:
-      if (!chk((size_t)N * A * KW * 4)) BAD();
-      for (int n = 0; n < N; n++) for (int a = 0; a < A; a++) for (int w = 0; w < KW; w++) RW(U[((size_t)n * A + a) * KW + w], blobs[n].known[a][w]);
-      if (scatter) for (int n = 0; n < N; n++) for (int sl = 0; sl < T; sl++) blobs[n].t_flags[sl] &= ~TF_KNOWN_ALL;  // caller-written masks: sense again
-      break;
-    case MUAVTA_F_THREAT_POS:
-      if (!chk((size_t)N * H * 2 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int h = 0; h < H; h++) { RW(D[((size_t)n * H + h) * 2], blobs[n].h_px[h]); RW(D[((size_t)n * H + h) * 2 + 1], blobs[n].h_py[h]); }
-      break;
-    case MUAVTA_F_THREAT_META:
-      if (!chk((size_t)N * H * 8 * 4)) BAD();
-      if (scatter) { e->err = "THREAT_META is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) for (int h = 0; h < H; h++) {
-        int32_t* r = I + ((size_t)n * H + h) * 8;
-        St& b = blobs[n];
-        r[0] = b.h_status[h]; r[1] = b.h_target[h]; r[2] = b.h_mission[h]; r[3] = b.h_acap[h]; r[4] = b.h_task_id[h]; r[5] = b.h_type[h];
-        r[6] = b.h_group[h]; r[7] = b.h_intercept[h];
-      }
-      break;
-    case MUAVTA_F_SCALARS:
-      if (!chk((size_t)N * MUAVTA_N_SCALARS * 8)) BAD();
-      if (scatter) { e->err = "SCALARS is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) {
-        St& b = blobs[n];
-        double* s = D + (size_t)n * MUAVTA_N_SCALARS;
-        s[0] = b.time_steps; s[1] = b.last_reward; s[2] = b.F_Reward; s[3] = b.total_distance; s[4] = b.n_on_time;
-        s[5] = b.n_missed_windows; s[6] = b.n_windowed_tasks; s[7] = b.n_task_switches; s[8] = b.n_reallocations;
-        s[9] = b.n_arrivals; s[10] = b.idle_reserve_steps; s[11] = b.conclusion_time; s[12] = b.escort_requests;
-        s[13] = b.escort_completed; s[14] = b.escort_failed; s[15] = b.escort_required_steps; s[16] = b.escort_covered_steps;
-        s[17] = b.protection_breaches; s[18] = b.threats_intercepted; s[19] = b.recon_losses; s[20] = b.escort_losses;
-        s[21] = b.mutual_support_engagements; s[22] = b.protected_rec_completed; s[23] = b.n_replans;
-        s[24] = b.pending_reset; s[25] = b.n_reached; s[26] = b.n_pending; s[27] = b.next_task_id - 1;
-      }
-      break;
-    case MUAVTA_F_OPEN_IDS:
-      if (!chk((size_t)N * T * 4)) BAD();
-      if (scatter) { e->err = "OPEN_IDS is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) for (int k = 0; k < T; k++) I[(size_t)n * T + k] = k < blobs[n].n_open ? blobs[n].t_id[blobs[n].open_slot[k]] : -1;
-      break;
-    case MUAVTA_F_EVENTS:
-      if (!chk((size_t)N * E * 2 * 4)) BAD();
-      if (scatter) { e->err = "EVENTS is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) for (int k = 0; k < E; k++) {
-        I[((size_t)n * E + k) * 2] = k < blobs[n].n_dev ? blobs[n].dev_tag[k] : -1;
-        I[((size_t)n * E + k) * 2 + 1] = k < blobs[n].n_dev ? blobs[n].dev_arg[k] : 0;
-      }
-      break;
-    case MUAVTA_F_EVENT_LIST:
-      if (!chk((size_t)N * E * 2 * 4)) BAD();
-      if (scatter) { e->err = "EVENT_LIST is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) for (int k = 0; k < E; k++) {
-        I[((size_t)n * E + k) * 2] = k < blobs[n].n_events ? blobs[n].ev_tag[k] : -1;
-        I[((size_t)n * E + k) * 2 + 1] = k < blobs[n].n_events ? blobs[n].ev_arg[k] : 0;
-      }
-      break;
-    case MUAVTA_F_STAGED_ACTIONS:
-      if (!chk((size_t)N * TL::A * 3 * 4)) BAD();
-      if (scatter) { e->err = "STAGED_ACTIONS is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) for (int k = 0; k < TL::A; k++) {
-        St& b = blobs[n];
-        int32_t* r = I + ((size_t)n * TL::A + k) * 3;
-        bool v = k < b.n_act;
-        r[0] = v ? b.act_agent[k] : -1; r[1] = v && b.act_slot[k] >= 0 ? b.t_id[b.act_slot[k]] : -1; r[2] = v ? b.act_index[k] : -1;
-      }
-      break;
-    case MUAVTA_F_ERROR:
-      if (!chk((size_t)N * 4)) BAD();
-      if (scatter) { e->err = "ERROR is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) I[n] = blobs[n].error;
-      break;
-    case MUAVTA_F_ESCORTS:
-      if (!chk((size_t)N * TL::A * 2 * 4)) BAD();
-      if (scatter) { e->err = "ESCORTS is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++) for (int k = 0; k < TL::A; k++) {
-        const bool v = k < blobs[n].n_escorts;
-        I[((size_t)n * TL::A + k) * 2] = v ? blobs[n].esc_agent[k] : -1;
-        I[((size_t)n * TL::A + k) * 2 + 1] = v ? blobs[n].esc_id[k] : -1;
-      }
-      break;
-    case MUAVTA_F_KNOWN_COUNT:
-      if (!chk((size_t)N * A * 4)) BAD();
-      if (scatter) { e->err = "KNOWN_COUNT is read-only"; return MUAVTA_E_ARG; }
-      for (int n = 0; n < N; n++)
-        for (int a = 0; a < A; a++) {
-          int c = blobs[n].a_gone[a];
-          for (int w = 0; w < TL::KW; w++) c += __builtin_popcount(blobs[n].known[a][w]);
-          I[(size_t)n * A + a] = c;
-        }
-      break;
-    default:
-      e->err = "unknown field";
-      return MUAVTA_E_ARG;
-  }
-#undef BAD
-#undef RW
-  return MUAVTA_OK;
-}
-
-template <class TL>
-void forget_obs_rows(MuavtaEnv* e) {  // the host rewrote the blobs: what the observation buffer holds no longer follows from them
-  EnvState<TL>* blobs = reinterpret_cast<EnvState<TL>*>(e->host_blobs.data());
-  for (int n = 0; n < e->n_envs; n++) blobs[n].obs_rows = -1;
-}
-
-template <class TL>
-int check_errors(MuavtaEnv* e) {  // scan the per-env error words after a synchronising call
-  typedef EnvState<TL> St;
-  St* blobs = reinterpret_cast<St*>(e->host_blobs.data());
-  for (int n = 0; n < e->n_envs; n++)
-    if (blobs[n].error) {
-      e->err = "env " + std::to_string(n) + " overflowed a tile (code " + std::to_string(blobs[n].error) +
-               ": 1=task slots 2=agent queue 3=events 4=pending reveals 5=random_position 6=escorts 7=lsap)";
-      return MUAVTA_E_CAPACITY;
-    }
-  return MUAVTA_OK;
-}
-
-}  // namespace
-
-// ---- state lanes ----------------------------------------------------------------------------------------------------------------------
-static void flip_lanes(MuavtaEnv* e) {  // the other lane's contents move into *e (and this one's into the twin)
-  MuavtaEnv* t = e->hl.twin;
-  std::swap(*e, *t);
-  std::swap(e->hl, t->hl);  // (handle-level state and the RCCL communicator stay with the handle the caller holds)
-  std::swap(e->comm, t->comm); std::swap(e->comm_rank, t->comm_rank); std::swap(e->comm_ranks, t->comm_ranks); std::swap(e->d_comm, t->d_comm);
-}
-static MuavtaEnv* lane_by_id(MuavtaEnv* e, int id) { return e->lane_id == id ? e : e->hl.twin; }
-static int ensure_twin(MuavtaEnv* e) {  // create the second lane (same configuration, allocator, sub-batches, release log)
-  if (e->hl.twin) return MUAVTA_OK;
-  if (e->hl.twin_failed) return MUAVTA_E_HIP;
-  MuavtaEnv* t = nullptr;
-  int rc = muavta_create(&e->params, e->n_envs, e->device, &t);
-  if (rc == MUAVTA_OK && e->n_parts) rc = muavta_set_parts(t, e->n_parts);
-  if (rc == MUAVTA_OK && e->d_rel) rc = muavta_set_release_log(t, 1);
-  if (rc != MUAVTA_OK) { if (t) muavta_destroy(t); e->hl.twin_failed = true; return rc; }
-  t->alloc_mode = e->alloc_mode;
-  if (e->hl.pol_set && push_policy(t, e->hl) != MUAVTA_OK) { e->err = t->err; muavta_destroy(t); e->hl.twin_failed = true; return MUAVTA_E_HIP; }
-  if (e->P.slot_cap && muavta_set_slot_cap(t, e->P.slot_cap) != MUAVTA_OK) { muavta_destroy(t); e->hl.twin_failed = true; return MUAVTA_E_HIP; }
-  // the waits the caller queued before this lane existed hold for it too (its part streams fork from its main stream at their first launch)
-  for (hipEvent_t ev : e->hl.pending_waits)
-    if (hipStreamWaitEvent(t->stream, ev, 0) != hipSuccess) { muavta_destroy(t); e->hl.twin_failed = true; return MUAVTA_E_HIP; }
-  for (hipEvent_t ev : e->hl.pending_waits) hipEventDestroy(ev);
-  e->hl.pending_waits.clear();
-  t->lane_id = e->lane_id ^ 1;
-  t->hl.lanes_mode = 1;  // (a twin never grows a twin)
-  e->hl.twin = t;
-  return MUAVTA_OK;
-}
-
-// ---- sub-batches on their own streams (muavta_set_parts) ------------------------------------------------------------------
-// Ordering between the handle's main stream and the part streams: an entry point that works on the main stream first makes it
-// wait for whatever the part streams still hold (join_parts) and flags every part to wait for the main stream before its next
-// launch (fork_part).  Both are event waits on the device: the host never blocks.
-static int join_parts(MuavtaEnv* e) {
-  for (int p = 0; p < e->n_parts; p++) {
-    if (e->part_busy[p]) {
-      HIPCHK(e, hipEventRecord(e->part_ev[p], e->part_stream[p]));
-      HIPCHK(e, hipStreamWaitEvent(e->stream, e->part_ev[p], 0));
-      e->part_busy[p] = false;
-    }
-    e->part_fork_needed[p] = true;
-  }
-  return MUAVTA_OK;
-}
-#define MAIN_OP(e) do { if ((e)->n_parts) { int rc_ = join_parts(e); if (rc_) return rc_; } } while (0)
-static int fork_part(MuavtaEnv* e, int p) {
-  if (e->part_fork_needed[p]) {
-    HIPCHK(e, hipEventRecord(e->ev_fork, e->stream));
-    HIPCHK(e, hipStreamWaitEvent(e->part_stream[p], e->ev_fork, 0));
-    e->part_fork_needed[p] = false;
-  }
-  e->part_busy[p] = true;
-  return MUAVTA_OK;
-}
-static void part_range(const MuavtaEnv* e, int p, int* first, int* count) {
-  const long long N = e->n_envs, k = e->n_parts > 0 ? e->n_parts : 1;
-  const int lo = (int)(N * p / k), hi = (int)(N * (p + 1) / k);
-  *first = lo; *count = hi - lo;
-}
-static int check_part(MuavtaEnv* e, int p, const char* who) {
-  if (!e) return MUAVTA_E_ARG;
-  if (e->n_parts < 1 || p < 0 || p >= e->n_parts) { e->err = std::string(who) + ": no such part (muavta_set_parts first)"; return MUAVTA_E_ARG; }
-  if (!e->did_reset) { e->err = std::string(who) + " before reset"; return MUAVTA_E_STATE; }
-  return MUAVTA_OK;
-}
-
-// muavta_set_pair_policy on ONE lane: the lane's copy of the weights, its scratch and the `pol` words of its context, on the lane's
-// stream behind whatever it (and its part streams) still runs; synchronised, so the host vector may change afterwards.
-static int push_policy(MuavtaEnv* l, const MuavtaEnv::HandleLevel& hl) {
-  DeviceScope scope_(l->device);
-  MAIN_OP(l);
-  PairPolicyDev pd;
-  memset(&pd, 0, sizeof(pd));
-  if (hl.pol_set) {
-    if (!l->d_pol_w) HIPCHK(l, hipMalloc((void**)&l->d_pol_w, (size_t)PW_FLOATS * sizeof(float)));
-    if (!l->d_pol_scratch) {
-      HIPCHK(l, hipMalloc((void**)&l->d_pol_scratch, (size_t)l->n_envs * PS_FLOATS * sizeof(float)));
-      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch, 0, (size_t)l->n_envs * PS_FLOATS * sizeof(float), l->stream));
-    }
-    HIPCHK(l, hipMemcpyAsync(l->d_pol_w, hl.pol_w.data(), (size_t)PW_FLOATS * sizeof(float), hipMemcpyHostToDevice, l->stream));
-    pd.w = l->d_pol_w; pd.scratch = l->d_pol_scratch; pd.raw = hl.pol_raw; pd.clamp = hl.pol_clamp;
-  }
-  HIPCHK(l, hipMemcpyAsync((char*)l->d_ctx + offsetof(DevCtx, pol), &pd, sizeof(pd), hipMemcpyHostToDevice, l->stream));
-  HIPCHK(l, hipStreamSynchronize(l->stream));  // `pd` is a stack object
-  return MUAVTA_OK;
-}
-
-// ====================================================================================================
-// C ABI
-// ====================================================================================================
-extern "C" {
-
-// sizeof() of the ABI structs, so a binding can verify its own layout: out[0] = MuavtaParams, out[1] = MuavtaDims
-int muavta_abi_sizes(int32_t* out) {
-  if (!out) return MUAVTA_E_ARG;
-  out[0] = (int32_t)sizeof(MuavtaParams);
-  out[1] = (int32_t)sizeof(MuavtaDims);
-  out[2] = MUAVTA_ABI_VERSION;
-  return MUAVTA_OK;
-}
-
-const char* muavta_last_error(const MuavtaEnv* env) { return env ? env->err.c_str() : g_create_error.c_str(); }
-
-int muavta_create(const MuavtaParams* params, int32_t n_envs, int32_t device, MuavtaEnv** out) {
-  if (!params || !out || n_envs < 1) { g_create_error = "muavta_create: bad arguments"; return MUAVTA_E_ARG; }
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    g_create_error = "muavta_create: no HIP device visible; this library is the MI355X path and has no CPU fallback";
-    return MUAVTA_E_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) { g_create_error = "muavta_create: device index out of range"; return MUAVTA_E_ARG; }
-  MuavtaEnv* e = new (std::nothrow) MuavtaEnv();
-  if (!e) { g_create_error = "out of memory"; return MUAVTA_E_ARG; }
-  int rc = fill_dev_params(params, &e->P, &g_create_error);
-  if (rc) { delete e; return rc; }
-  e->params = *params;
-  e->n_envs = n_envs;
-  e->device = device;
-  int ta = params->tile_agents > e->P.n_agents ? params->tile_agents : e->P.n_agents;
-  int tt = params->tile_tasks > 0 ? params->tile_tasks : 0;
-  int th = params->tile_threats > e->P.n_threats ? params->tile_threats : e->P.n_threats;
-  if (ta <= Tile16::A && tt <= Tile16::T && th <= Tile16::H) e->tile = TK16;
-  else if (ta <= Tile24::A && tt <= Tile24::T && th <= Tile24::H) e->tile = TK24;
-  else if (ta <= Tile64::A && tt <= Tile64::T && th <= Tile64::H) e->tile = TK64;
-  else { g_create_error = "muavta_create: requested tile exceeds 64 agents x 128 task slots x 48 threats"; delete e; return MUAVTA_E_ARG; }
-  size_t scratch_bytes = 0;
-  e->P.slot_cap = 0;  // (live slots an env may use: the tile's; muavta_set_slot_cap lowers it for capacity tests)
-  DISPATCH(e, { e->A = TL::A; e->T = TL::T; e->H = TL::H; e->E = TL::E; e->R = TL::R; e->Q = TL::Q; e->state_bytes = sizeof(EnvState<TL>);
-                e->cold_bytes = sizeof(EnvCold<TL>); scratch_bytes = sizeof(Scratch<TL>); });
-  (void)scratch_bytes;
-#define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_create_error = std::string(#expr) + ": " + hipGetErrorString(e_); muavta_destroy(e); return MUAVTA_E_HIP; } } while (0)
-  DeviceScope scope_(device);
-  CK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  for (int i = 0; i < MuavtaEnv::EV_RING; i++) { CK(hipEventCreate(&e->ev0[i])); CK(hipEventCreate(&e->ev1[i])); }
-  CK(hipStreamCreateWithFlags(&e->seed_stream, hipStreamNonBlocking));
-  for (int b = 0; b < 2; b++) {
-    CK(hipEventCreate(&e->ev_seed0[b])); CK(hipEventCreate(&e->ev_seeded[b])); CK(hipEventCreateWithFlags(&e->ev_consumed[b], hipEventDisableTiming));
-  }
-  // The sub-batch streams (muavta_set_parts) are created HERE, right behind the main and the seeding stream, and touched once:
-  // HIP binds a stream to one of its few hardware queues (GPU_MAX_HW_QUEUES, 4 by default) when the stream first gets work,
-  // taking the least-loaded queue, and two streams on one queue execute in order.  Created lazily in the middle of a process'
-  // life (after the framework's own streams, copy engines ...) two part streams could land on ONE queue: measured r3, two
-  // sub-batches ran at 46 M env-steps/s inside bench.py against 70 M in a fresh process, with identical kernels.
-  // (r4) Opt-in: MUAVTA_EAGER_PART_STREAMS=n (0..8, default 0) creates n of them here; the rest are created by muavta_set_parts when
-  // they are first asked for.  A handle that never uses sub-batches owns two streams, not ten.
-  {
-    const char* ev = getenv("MUAVTA_EAGER_PART_STREAMS");
-    int eager = ev ? atoi(ev) : 0;
-    eager = eager < 0 ? 0 : eager > MuavtaEnv::MAX_PARTS ? MuavtaEnv::MAX_PARTS : eager;
-    for (int p = 0; p < eager; p++) {
-      CK(hipStreamCreateWithFlags(&e->part_stream[p], hipStreamNonBlocking));
-      CK(hipEventCreateWithFlags(&e->part_ev[p], hipEventDisableTiming));
-      CK(hipEventRecord(e->part_ev[p], e->part_stream[p]));
-    }
-  }
-  CK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-  const size_t N = (size_t)n_envs, mt = (size_t)e->P.max_tasks, nA = (size_t)e->P.n_agents;
-  CK(hipMalloc(&e->blobs, N * e->state_bytes));
-  CK(hipMemsetAsync(e->blobs, 0, N * e->state_bytes, e->stream));
-  CK(hipMalloc(&e->cold, N * e->cold_bytes));
-  CK(hipMemsetAsync(e->cold, 0, N * e->cold_bytes, e->stream));
-  CK(hipMalloc(&e->tapes, N * MUAVTA_RNG_STREAMS * MUAVTA_RNG_WORDS * sizeof(uint32_t)));
-  // zeroed like the blobs: without obstacles the obs stream is never seeded, yet every step prefetches its next eight words into
-  // rng_win — whatever the allocation held would end up in get_state / get_rng, different from one handle to the next
-  CK(hipMemsetAsync(e->tapes, 0, N * MUAVTA_RNG_STREAMS * MUAVTA_RNG_WORDS * sizeof(uint32_t), e->stream));
-  for (int b = 0; b < 2; b++) {
-    CK(hipMalloc(&e->d_seeds[b], N * sizeof(uint64_t)));
-    CK(hipHostMalloc((void**)&e->h_seeds[b], N * sizeof(uint64_t), hipHostMallocDefault));
-  }
-  CK(hipMalloc(&e->d_act_agent, N * e->A * sizeof(int32_t)));
-  CK(hipMalloc(&e->d_act_index, N * e->A * sizeof(int32_t)));
-  CK(hipMalloc(&e->d_metrics, N * MUAVTA_N_METRICS * sizeof(double)));
-  CK(hipMalloc(&e->O.tasks, N * mt * 21 * sizeof(float)));
-  CK(hipMalloc(&e->O.legal, N * nA * ((mt + 63) / 64) * sizeof(unsigned long long)));
-  CK(hipMalloc(&e->O.pad, N * mt));
-  CK(hipMalloc(&e->O.agents, N * nA * 9 * sizeof(float)));
-  CK(hipMalloc(&e->O.flags, N * 5 * sizeof(float)));
-  CK(hipMalloc(&e->O.reward, N * sizeof(double)));
-  CK(hipMalloc(&e->O.done, N));
-  {
-    DevCtx h;
-    memset(&h, 0, sizeof(h));
-    CK(hipMalloc((void**)&e->d_pace, (size_t)PACE_KEYS * 16 * sizeof(uint32_t)));
-    CK(hipMemsetAsync(e->d_pace, 0, (size_t)PACE_KEYS * 16 * sizeof(uint32_t), e->stream));  // epoch 0 is never issued
-    h.P = e->P; h.O = e->O; h.tapes = e->tapes; h.blobs = e->blobs; h.cold = e->cold; h.pace = e->d_pace;
-    CK(hipMalloc(&e->d_rec, 2 * MuavtaEnv::REC_SLOT));
-    CK(hipMemsetAsync(e->d_rec, 0, 2 * MuavtaEnv::REC_SLOT, e->stream));
-    CK(hipMalloc((void**)&e->d_ctx, sizeof(DevCtx)));
-    CK(hipMemcpyAsync(e->d_ctx, &h, sizeof(DevCtx), hipMemcpyHostToDevice, e->stream));
-    CK(hipStreamSynchronize(e->stream));  // `h` is a stack object
-  }
-#undef CK
-  int arc = MUAVTA_OK;
-  DISPATCH(e, arc = launch_attr<TL>(e));
-  if (arc) { g_create_error = e->err; muavta_destroy(e); return arc; }
-  *out = e;
-  return MUAVTA_OK;
-}
-
-int muavta_destroy(MuavtaEnv* e) {
-  if (!e) return MUAVTA_OK;
-  muavta_comm_destroy(e);
-  if (e->hl.twin) { muavta_destroy(e->hl.twin); e->hl.twin = nullptr; }
-  DeviceScope scope_(e->device);
-  for (hipEvent_t ev : e->hl.pending_waits) hipEventDestroy(ev);
-  e->hl.pending_waits.clear();
-  if (e->seed_stream) hipStreamSynchronize(e->seed_stream);
-  for (int p = 0; p < MuavtaEnv::MAX_PARTS; p++) {
-    if (e->part_stream[p]) { hipStreamSynchronize(e->part_stream[p]); hipStreamDestroy(e->part_stream[p]); }
-    if (e->part_ev[p]) hipEventDestroy(e->part_ev[p]);
-  }
-  if (e->ev_fork) hipEventDestroy(e->ev_fork);
-  hipFree(e->d_part_agent); hipFree(e->d_part_index); if (e->d_run) hipFree(e->d_run);
-  if (e->stream) hipStreamSynchronize(e->stream);
-  if (e->d_seedtmp) hipFree(e->d_seedtmp); hipFree(e->blobs); hipFree(e->cold); hipFree(e->tapes); hipFree(e->d_ctx); hipFree(e->d_pace); if (e->d_rec) hipFree(e->d_rec); for (int b = 0; b < 2; b++) { hipFree(e->d_seeds[b]); if (e->d_seedbuf[b]) hipFree(e->d_seedbuf[b]); if (e->h_seeds[b]) hipHostFree(e->h_seeds[b]); } hipFree(e->d_act_agent); hipFree(e->d_act_index); if (e->d_list_agent) hipFree(e->d_list_agent); if (e->d_list_index) hipFree(e->d_list_index); hipFree(e->d_call_out); hipFree(e->d_metrics); if (e->d_pol_w) hipFree(e->d_pol_w); if (e->d_pol_scratch) hipFree(e->d_pol_scratch); if (e->d_tok) hipFree(e->d_tok); if (e->d_rel) hipFree(e->d_rel);
-  hipFree(e->O.tasks); hipFree(e->O.legal); hipFree(e->O.pad); hipFree(e->O.agents); hipFree(e->O.flags); hipFree(e->O.reward); hipFree(e->O.done);
-  for (int i = 0; i < MuavtaEnv::EV_RING; i++) { if (e->ev0[i]) hipEventDestroy(e->ev0[i]); if (e->ev1[i]) hipEventDestroy(e->ev1[i]); }
-  for (int b = 0; b < 2; b++) {
-    if (e->ev_seed0[b]) hipEventDestroy(e->ev_seed0[b]);
-    if (e->ev_seeded[b]) hipEventDestroy(e->ev_seeded[b]);
-    if (e->ev_consumed[b]) hipEventDestroy(e->ev_consumed[b]);
-  }
-  if (e->seed_stream) hipStreamDestroy(e->seed_stream);
-  if (e->stream) hipStreamDestroy(e->stream);
-  delete e;
-  return MUAVTA_OK;
-}
-
-int muavta_dims(const MuavtaEnv* e, MuavtaDims* d) {
-  if (!e || !d) return MUAVTA_E_ARG;
-  d->n_envs = e->n_envs; d->n_agents = e->P.n_agents; d->tile_agents = e->A; d->tile_tasks = e->T; d->tile_threats = e->H;
-  d->max_tasks = e->P.max_tasks; d->obs_task_width = 21; d->obs_agent_width = 9; d->queue_cap = e->Q; d->event_cap = e->E;
-  d->action_cap = e->A; d->state_bytes = (int64_t)(e->state_bytes + e->cold_bytes);
-  d->n_threats = e->P.n_threats; d->known_words = (e->T + 31) / 32; d->lds_bytes = (int32_t)e->lds_bytes; d->legal_words = (e->P.max_tasks + 63) / 64;
-  return MUAVTA_OK;
-}
-
-// Upload `seeds` and run the seeding kernel on the seed stream into the next slot; the handle's stream waits for it.
-// The caller launches the consumer on e->stream and then calls seeding_consumed(e, slot).
-static int enqueue_seeding(MuavtaEnv* e, const uint64_t* seeds, const uint64_t** ds, const uint32_t** sb, int* slot) {
-  const size_t N = (size_t)e->n_envs;
-  const int b = (int)(e->seed_seq & 1u);  // (the slot sequence only advances once the kernel is queued: a failed call leaves it alone)
-  if (e->seed_used[b]) {
-    HIPCHK(e, hipEventSynchronize(e->ev_seeded[b]));                        // the staging copy of two calls ago has left h_seeds[b]
-    HIPCHK(e, hipStreamWaitEvent(e->seed_stream, e->ev_consumed[b], 0));    // ... and its consumer has read d_seeds / d_seedbuf[b]
-  }
-  memcpy(e->h_seeds[b], seeds, N * sizeof(uint64_t));
-  HIPCHK(e, hipMemcpyAsync(e->d_seeds[b], e->h_seeds[b], N * sizeof(uint64_t), hipMemcpyHostToDevice, e->seed_stream));
-  const size_t seed_bytes = ((N + 15) / 16) * WG * 624 * sizeof(uint32_t);  // whole waves of 16 envs x 4 streams
-  if (!e->d_seedbuf[b]) HIPCHK(e, hipMalloc((void**)&e->d_seedbuf[b], seed_bytes));
-  if (!e->d_seedtmp) HIPCHK(e, hipMalloc((void**)&e->d_seedtmp, seed_bytes));  // k_seed's scratch (one: its launches are serialised on the seed stream)
-  HIPCHK(e, hipEventRecord(e->ev_seed0[b], e->seed_stream));
-  hipLaunchKernelGGL(k_seed, dim3((unsigned)((N + 15) / 16)), dim3(WG), 0, e->seed_stream, (const uint64_t*)e->d_seeds[b], (int)N,
-                     (int)(e->P.num_obstacles > 0), e->d_seedbuf[b], e->d_seedtmp);
-  HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipEventRecord(e->ev_seeded[b], e->seed_stream));
-  HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_seeded[b], 0));
-  e->seed_used[b] = true;
-  e->seed_seq++;
-  e->last_seed_slot = b;
-  *ds = e->d_seeds[b]; *sb = e->d_seedbuf[b]; *slot = b;
-  return MUAVTA_OK;
-}
-static int seeding_consumed(MuavtaEnv* e, int slot) {
-  HIPCHK(e, hipEventRecord(e->ev_consumed[slot], e->stream));
-  return MUAVTA_OK;
-}
-
-int muavta_reset(MuavtaEnv* e, const uint64_t* seeds) {
-  if (!e || !seeds) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  const uint64_t* ds = nullptr;
-  const uint32_t* sb = nullptr;
-  int slot = 0;
-  { int rc = enqueue_seeding(e, seeds, &ds, &sb, &slot); if (rc) return rc; }
-  DISPATCH(e, hipLaunchKernelGGL(k_reset<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, ds, sb));
-  HIPCHK(e, hipGetLastError());
-  { int rc = seeding_consumed(e, slot); if (rc) return rc; }
-  e->last_seeded = true;  // muavta_last_seed_ms reports this reset's k_seed
-  e->did_reset = true;
-  e->host_valid = false;
-  return MUAVTA_OK;
-}
-
-static int step_impl(MuavtaEnv* e, const int32_t* aa, const int32_t* ai, int cap = 0) {
-  if (!e->did_reset) { e->err = "step before reset"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  const int32_t *da = nullptr, *di = nullptr;
-  if (cap <= 0) cap = e->A;
-  if (aa) {
-    size_t bytes = (size_t)e->n_envs * cap * sizeof(int32_t);
-    int32_t *ba = e->d_act_agent, *bi = e->d_act_index;
-    if (cap > e->A) {  // rows longer than the handle's action buffers: muavta_step_lists
-      if (cap > e->list_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (e->d_list_agent) hipFree(e->d_list_agent);
-        if (e->d_list_index) hipFree(e->d_list_index);
-        e->d_list_agent = e->d_list_index = nullptr; e->list_cap = 0;
-        HIPCHK(e, hipMalloc(&e->d_list_agent, bytes));
-        HIPCHK(e, hipMalloc(&e->d_list_index, bytes));
-        e->list_cap = cap;
-      }
-      ba = e->d_list_agent; bi = e->d_list_index;
-    }
-    HIPCHK(e, hipMemcpyAsync(ba, aa, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(bi, ai, bytes, hipMemcpyHostToDevice, e->stream));
-    da = ba; di = bi;
-  }
-  if (e->d_rel) HIPCHK(e, hipMemsetAsync(e->d_rel, 0, (size_t)e->n_envs * (1 + MUAVTA_REL_ROW * e->T) * sizeof(double), e->stream));
-  DISPATCH(e, hipLaunchKernelGGL(k_step<TL>, dim3(e->n_envs), dim3(WG), 0, e->stream, (const DevCtx*)e->d_ctx, da, di, cap, e->d_rel, 0));  // (static LDS)
-  HIPCHK(e, hipGetLastError());
-  e->host_valid = false;
-  return MUAVTA_OK;
-}
-
-int muavta_step_lists(MuavtaEnv* e, const int32_t* act_agent, const int32_t* act_index, int32_t list_cap) {
-  if (!e || !act_agent || !act_index) return MUAVTA_E_ARG;
-  if (list_cap < 1 || list_cap > 32767) { e->err = "muavta_step_lists: list_cap must be in 1..32767"; return MUAVTA_E_ARG; }
-  // agent ids index the per-agent arrays of the env blob on the device: reject anything outside [0, n_agents) up front
-  // (the reference's actions dict is keyed by agent name: an unknown name is a KeyError there, DroneEnv.py:813-816)
-  for (int n = 0; n < e->n_envs; n++)
-    for (int k = 0; k < list_cap; k++) {
-      const int a = act_agent[(size_t)n * list_cap + k];
-      if (a < 0) break;
-      if (a >= e->P.n_agents) {
-        e->err = "muavta_step: env " + std::to_string(n) + " names agent id " + std::to_string(a) + ", valid ids are 0.." + std::to_string(e->P.n_agents - 1);
-        return MUAVTA_E_ARG;
-      }
-    }
-  return step_impl(e, act_agent, act_index, list_cap);
-}
-int muavta_step(MuavtaEnv* e, const int32_t* act_agent, const int32_t* act_index) {
-  if (!e) return MUAVTA_E_ARG;
-  return muavta_step_lists(e, act_agent, act_index, e->A);
-}
-int muavta_step_staged(MuavtaEnv* e) {
-  if (!e) return MUAVTA_E_ARG;
-  return step_impl(e, nullptr, nullptr);
-}
-
-int muavta_allocate(MuavtaEnv* e, int32_t interval, int32_t use_vis, int32_t* act_agent, int32_t* act_index) {
-  if (!e) return MUAVTA_E_ARG;
-  if (!e->did_reset) { e->err = "allocate before reset"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR)
-    DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, false, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes() + SCORED_EXTRA_LDS, e->stream, (const DevCtx*)e->d_ctx,
-                                   interval, use_vis, e->alloc_mode, e->d_act_agent, e->d_act_index, e->A, 0))
-  else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY)
-    DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, interval, use_vis,
-                                   e->alloc_mode, e->d_act_agent, e->d_act_index, e->A, 0))
-  else
-    DISPATCH(e, hipLaunchKernelGGL(k_allocate<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, interval, use_vis, e->alloc_mode,
-                                   e->d_act_agent, e->d_act_index, e->A, 0));
-  HIPCHK(e, hipGetLastError());
-  e->host_valid = false;
-  if (act_agent && act_index) {
-    size_t bytes = (size_t)e->n_envs * e->A * sizeof(int32_t);
-    HIPCHK(e, hipMemcpyAsync(act_agent, e->d_act_agent, bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(act_index, e->d_act_index, bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-  }
-  return MUAVTA_OK;
-}
-
-static int token_dims(int kind, int* dt, int* da);
-
-// ---- HungarianAllocator.allocate_tasks with the caller's edge scores / priorities / reserved agents ------------------------------
-static int scored_check(MuavtaEnv* e, const MuavtaScored* sp) {
-  int dt, da;
-  if (!e) return MUAVTA_E_ARG;
-  if (!sp || token_dims(sp->kind, &dt, &da) || sp->max_tasks < 1 || sp->max_tasks > 128 || sp->max_agents < 1 || sp->max_agents > 64 ||
-      sp->gate < MUAVTA_GATE_FORCE || sp->gate > MUAVTA_GATE_ALLOCATOR || (sp->flags & ~7) ||
-      (sp->kind == MUAVTA_TOK_ESCORT && (sp->flags & MUAVTA_SC_FULL_TASK_LIST))) {
-    e->err = "muavta_allocate_scored: bad spec (kind 0..2, max_tasks 1..128, max_agents 1..64, gate 0..3, flags 0..7; build_escort_tokens has no untruncated list)";
-    return MUAVTA_E_ARG;
-  }
-  if (!e->did_reset) { e->err = "allocate before reset"; return MUAVTA_E_STATE; }
-  return MUAVTA_OK;
-}
-int muavta_allocate_scored_device(MuavtaEnv* e, const MuavtaScored* sp) {
-  if (int rc = scored_check(e, sp)) return rc;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  ScoredDev sc{sp->edge_scores, sp->task_pri, (const unsigned long long*)sp->reserved, sp->selected, sp->replanned, sp->kind, sp->max_tasks,
-               sp->max_agents, sp->gate, sp->flags};
-  DISPATCH(e, hipLaunchKernelGGL(k_allocate_scored<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes() + SCORED_EXTRA_LDS, e->stream, (const DevCtx*)e->d_ctx, sc,
-                                 sp->replan_interval, sp->use_visibility, e->d_act_agent, e->d_act_index, e->A, 0));
-  HIPCHK(e, hipGetLastError());
-  e->host_valid = false;
-  return MUAVTA_OK;
-}
-int muavta_allocate_scored(MuavtaEnv* e, const MuavtaScored* sp, int32_t* act_agent, int32_t* act_index) {
-  if (int rc = scored_check(e, sp)) return rc;
-  DeviceScope scope_(e->device);
-  const size_t N = (size_t)e->n_envs, MT = (size_t)sp->max_tasks, MA = (size_t)sp->max_agents;
-  const size_t sz[5] = {N * MA * MT * 4, N * MT * 8, N * 8, N * MA * MT * 4, N * 4};  // scores, pri, reserved | selected, replanned
-  size_t off[6] = {0};
-  for (int i = 0; i < 5; i++) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
-  if (off[5] > e->tok_bytes) {  // (shares the staging buffer of muavta_tokens' host variant)
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (e->d_tok) hipFree(e->d_tok);
-    e->d_tok = nullptr; e->tok_bytes = 0;
-    HIPCHK(e, hipMalloc(&e->d_tok, off[5]));
-    e->tok_bytes = off[5];
-  }
-  char* b = (char*)e->d_tok;
-  const void* in[3] = {sp->edge_scores, sp->task_pri, sp->reserved};
-  for (int i = 0; i < 3; i++)
-    if (in[i]) HIPCHK(e, hipMemcpyAsync(b + off[i], in[i], sz[i], hipMemcpyHostToDevice, e->stream));
-  MuavtaScored d = *sp;
-  d.edge_scores = sp->edge_scores ? (const float*)(b + off[0]) : nullptr;
-  d.task_pri = sp->task_pri ? (const double*)(b + off[1]) : nullptr;
-  d.reserved = sp->reserved ? (const uint64_t*)(b + off[2]) : nullptr;
-  d.selected = sp->selected ? (float*)(b + off[3]) : nullptr;
-  d.replanned = sp->replanned ? (int32_t*)(b + off[4]) : nullptr;
-  if (int rc = muavta_allocate_scored_device(e, &d)) return rc;
-  if (sp->selected) HIPCHK(e, hipMemcpyAsync(sp->selected, b + off[3], sz[3], hipMemcpyDeviceToHost, e->stream));
-  if (sp->replanned) HIPCHK(e, hipMemcpyAsync(sp->replanned, b + off[4], sz[4], hipMemcpyDeviceToHost, e->stream));
-  if (act_agent && act_index) {
-    size_t bytes = N * e->A * sizeof(int32_t);
-    HIPCHK(e, hipMemcpyAsync(act_agent, e->d_act_agent, bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(act_index, e->d_act_index, bytes, hipMemcpyDeviceToHost, e->stream));
-  }
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-int muavta_rl_step_device(MuavtaEnv* e, const MuavtaRlStep* rs) {
-  if (!e || !rs) return MUAVTA_E_ARG;
-  const MuavtaScored* sp = &rs->plan;
-  if (int rc = scored_check(e, sp)) return rc;
-  const bool tok = rs->task_feats != nullptr;
-  if (tok && (!rs->task_mask || !rs->task_ids || !rs->agent_feats || !rs->agent_mask || !rs->agent_ids || !rs->edge_valid)) {
-    e->err = "muavta_rl_step_device: the next-token outputs come all together or not at all (n_urgent alone is optional)"; return MUAVTA_E_ARG;
-  }
-  DeviceScope scope_(e->device);
-  if (e->d_rel) { e->err = "muavta_rl_step_device: the release log must be off (muavta_set_release_log)"; return MUAVTA_E_STATE; }
-  ScoredDev sc{sp->edge_scores, sp->task_pri, (const unsigned long long*)sp->reserved, sp->selected, sp->replanned, sp->kind, sp->max_tasks,
-               sp->max_agents, sp->gate, sp->flags};
-  hipStream_t stream = e->stream;
-  int first = 0, count = e->n_envs;
-  if (rs->part > 0) {  // one sub-batch on its own stream (muavta_set_parts): the tensors are the whole batch's, the launch touches the part's rows
-    const int part = rs->part - 1;
-    { int rc = check_part(e, part, "muavta_rl_step_device"); if (rc) return rc; }
-    { int rc = fork_part(e, part); if (rc) return rc; }
-    part_range(e, part, &first, &count);
-    stream = e->part_stream[part];
-  } else {
-    MAIN_OP(e);
-  }
-  DISPATCH(e, launch_rl_step<TL>(e, sc, rs, stream, first, count));
-  HIPCHK(e, hipGetLastError());
-  e->host_valid = false;
-  return MUAVTA_OK;
-}
-// Run to the next replan gate (k_run; include/muavta.h): the policy in the loop, consulted only where an env's gate fired
-int muavta_rl_run_device(MuavtaEnv* e, const MuavtaRlRun* rr) {
-  if (!e || !rr) return MUAVTA_E_ARG;
-  const MuavtaRlStep* rs = &rr->first;
-  const MuavtaScored* sp = &rs->plan;
-  if (int rc = scored_check(e, sp)) return rc;
-  const bool tok = rs->task_feats != nullptr, ptok = rr->park_task_feats != nullptr;
-  if ((tok && (!rs->task_mask || !rs->task_ids || !rs->agent_feats || !rs->agent_mask || !rs->agent_ids || !rs->edge_valid)) ||
-      (ptok && (!rr->park_task_mask || !rr->park_task_ids || !rr->park_agent_feats || !rr->park_agent_mask || !rr->park_agent_ids || !rr->park_edge_valid))) {
-    e->err = "muavta_rl_run_device: the token outputs (next / park) come all together or not at all (n_urgent alone is optional)"; return MUAVTA_E_ARG;
-  }
-  if (rr->max_steps < 0) { e->err = "muavta_rl_run_device: max_steps >= 0 (0: until the gate fires or the episode ends)"; return MUAVTA_E_ARG; }
-  DeviceScope scope_(e->device);
-  if (e->d_rel) { e->err = "muavta_rl_run_device: the release log must be off (muavta_set_release_log)"; return MUAVTA_E_STATE; }
-  ScoredDev sc{sp->edge_scores, sp->task_pri, (const unsigned long long*)sp->reserved, sp->selected, sp->replanned, sp->kind, sp->max_tasks,
-               sp->max_agents, sp->gate, sp->flags};
-  hipStream_t stream = e->stream;
-  int first = 0, count = e->n_envs;
-  if (rs->part > 0) {
-    const int part = rs->part - 1;
-    { int rc = check_part(e, part, "muavta_rl_run_device"); if (rc) return rc; }
-    { int rc = fork_part(e, part); if (rc) return rc; }
-    part_range(e, part, &first, &count);
-    stream = e->part_stream[part];
-  } else {
-    MAIN_OP(e);
-  }
-  RunOut R{rs->s_wps, rs->done, rr->n_stepped, rr->park, rr->reward_sum};
-  DISPATCH(e, launch_run<TL>(e, RUN_SRC_SCORED, sc, rs, rr, R, sp->gate, sp->replan_interval, sp->use_visibility, rs->write_obs, rr->max_steps, nullptr, nullptr, 0, stream, first, count));
-  HIPCHK(e, hipGetLastError());
-  e->host_valid = false;
-  return MUAVTA_OK;
-}
-int muavta_step_run(MuavtaEnv* e, const int32_t* act_agent, const int32_t* act_index, int32_t gate, int32_t interval, int32_t max_steps, int32_t write_obs,
-                    int32_t* n_stepped, uint8_t* park, double* reward_sum) {
-  if (!e) return MUAVTA_E_ARG;
-  if (!e->did_reset) { e->err = "muavta_step_run before reset"; return MUAVTA_E_STATE; }
-  if ((act_agent == nullptr) != (act_index == nullptr) || gate < MUAVTA_GATE_FORCE || gate > MUAVTA_GATE_ALLOCATOR || max_steps < 0) {
-    e->err = "muavta_step_run: action rows come as a pair (or both NULL: the staged plan), gate 0..3, max_steps >= 0"; return MUAVTA_E_ARG;
-  }
-  if (act_agent)
-    for (int n = 0; n < e->n_envs; n++)
-      for (int k = 0; k < e->A; k++) {
-        const int a = act_agent[(size_t)n * e->A + k];
-        if (a < 0) break;
-        if (a >= e->P.n_agents) { e->err = "muavta_step_run: env " + std::to_string(n) + " names agent id " + std::to_string(a); return MUAVTA_E_ARG; }
-      }
-  DeviceScope scope_(e->device);
-  if (e->d_rel) { e->err = "muavta_step_run: the release log must be off (muavta_set_release_log)"; return MUAVTA_E_STATE; }
-  MAIN_OP(e);
-  const size_t N = (size_t)e->n_envs;
-  if (!e->d_run) HIPCHK(e, hipMalloc(&e->d_run, N * 16));
-  double* d_rsum = (double*)e->d_run; int32_t* d_n = (int32_t*)(d_rsum + N); uint8_t* d_park = (uint8_t*)(d_n + N);
-  const int32_t *da = nullptr, *di = nullptr;
-  if (act_agent) {
-    const size_t bytes = N * e->A * sizeof(int32_t);
-    HIPCHK(e, hipMemcpyAsync(e->d_act_agent, act_agent, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->d_act_index, act_index, bytes, hipMemcpyHostToDevice, e->stream));
-    da = e->d_act_agent; di = e->d_act_index;
-  }
-  ScoredDev sc{};
-  RunOut R{nullptr, nullptr, d_n, d_park, d_rsum};
-  DISPATCH(e, launch_run<TL>(e, act_agent ? RUN_SRC_ROWS : RUN_SRC_STAGED, sc, nullptr, nullptr, R, gate, interval, 0, write_obs, max_steps, da, di, e->A, e->stream, 0, e->n_envs));
-  HIPCHK(e, hipGetLastError());
-  e->host_valid = false;
-  if (n_stepped) HIPCHK(e, hipMemcpyAsync(n_stepped, d_n, N * 4, hipMemcpyDeviceToHost, e->stream));
-  if (park) HIPCHK(e, hipMemcpyAsync(park, d_park, N, hipMemcpyDeviceToHost, e->stream));
-  if (reward_sum) HIPCHK(e, hipMemcpyAsync(reward_sum, d_rsum, N * 8, hipMemcpyDeviceToHost, e->stream));
-  if (n_stepped || park || reward_sum) HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-}  // extern "C" (the launcher below is a template)
-template <class TL>
-static void launch_rollout(MuavtaEnv* e, const uint64_t* ds, int n_steps, int interval, int use_vis, int write_obs, const uint32_t* sb, size_t extra_lds,
-                           const MuavtaRecord* rec, hipStream_t stream, int env_base, int n_launch) {
-  RecordPtrs<TL> R;
-  memset(&R, 0, sizeof(R));
-  const int epoch = (int)(e->pace_epoch++ % 65535u) + 1;  // 1..65535: the zero-filled table matches no launch
-  if (rec) {
-    if (rec->kind >= 0) {
-      typename Sim<TL>::TokPtrs K{rec->task_feats, rec->task_mask, rec->task_ids, rec->agent_feats, rec->agent_mask, rec->agent_ids, rec->edge_valid,
-                                  rec->n_urgent, rec->expert_mask, rec->replanned, rec->kind, rec->max_tasks, rec->max_agents};
-      R.K = K; R.s_wps = rec->s_wps;
-    }
-    if (rec->obs_tasks) {
-      R.O.tasks = rec->obs_tasks; R.O.legal = (unsigned long long*)rec->obs_legal; R.O.pad = rec->obs_pad; R.O.agents = rec->obs_agents;
-      R.O.flags = rec->obs_flags; R.O.reward = rec->obs_reward; R.O.done = rec->obs_done;
-    }
-    R.n_envs = e->n_envs;
-    static_assert(sizeof(RecordPtrs<TL>) <= MuavtaEnv::REC_SLOT, "record-pointer slot too small");
-    // The slot is filled by a one-lane kernel that takes the struct BY VALUE (kernel arguments are captured when the launch is queued)
-    // — stream-ordered behind the previous launch that read the slot.  NOT hipMemcpyAsync from this stack frame: for pageable memory the
-    // runtime may pin the pages and copy after the call has returned, by when the frame is gone (first r4 build: wild ring pointers).
-    RecBlob blob;
-    memset(&blob, 0, sizeof(blob));
-    memcpy(&blob, &R, sizeof(R));
-    hipLaunchKernelGGL(k_store_rec, dim3(1), dim3(64), 0, stream, blob, (uint32_t*)((char*)e->d_rec + MuavtaEnv::REC_SLOT));
-    hipLaunchKernelGGL((k_rollout<TL, true>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
-                       n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)((char*)e->d_rec + MuavtaEnv::REC_SLOT), epoch, env_base);
-  } else if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) {
-    hipLaunchKernelGGL((k_rollout<TL, false, false, true>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
-                       n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)e->d_rec, epoch, env_base);
-  } else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) {
-    hipLaunchKernelGGL((k_rollout<TL, false, true>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
-                       n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)e->d_rec, epoch, env_base);
-  } else {
-    hipLaunchKernelGGL((k_rollout<TL, false>), dim3(n_launch), dim3(WG), extra_lds, stream, (const DevCtx*)e->d_ctx, ds,
-                       n_steps, interval, use_vis, e->alloc_mode, write_obs, e->d_metrics, sb, (const RecordPtrs<TL>*)e->d_rec, epoch, env_base);
-  }
-}
-extern "C" {
-static int rollout_impl(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, int32_t interval, int32_t use_vis, int32_t write_obs, const MuavtaRecord* rec) {
-  if (!e || n_steps < 0) return MUAVTA_E_ARG;
-  if (!seeds && !e->did_reset) { e->err = "rollout without seeds before reset"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  if (seeds && e->hl.lanes_mode != 1) {
-    // a fresh episode batch while this lane's last rollout is still running (or always, in mode 2): it goes to the other lane
-    bool want = e->hl.lanes_mode == 2;
-    if (!want && e->n_rollouts) { want = hipEventQuery(e->ev1[(e->n_rollouts - 1) % MuavtaEnv::EV_RING]) == hipErrorNotReady; (void)hipGetLastError(); }
-    if (want && ensure_twin(e) == MUAVTA_OK) flip_lanes(e);
-  }
-  MAIN_OP(e);
-  const uint64_t* ds = nullptr;
-  const uint32_t* sb = nullptr;
-  int slot = -1;
-  if (seeds) { int rc = enqueue_seeding(e, seeds, &ds, &sb, &slot); if (rc) return rc; }
-  e->last_seeded = ds != nullptr;
-  // muavta_rollout_record's obs_done pre-fill: on the stream of the lane that runs the kernel, so only after the lane decision above
-  if (rec && rec->obs_done && n_steps > 0)
-    HIPCHK(e, hipMemsetAsync(rec->obs_done, MUAVTA_OBS_UNWRITTEN, (size_t)n_steps * (size_t)e->n_envs, e->stream));
-  const int evi = (int)(e->n_rollouts % MuavtaEnv::EV_RING);
-  HIPCHK(e, hipEventRecord(e->ev0[evi], e->stream));
-  static const size_t extra_lds = getenv("MUAVTA_EXTRA_LDS") ? (size_t)atoi(getenv("MUAVTA_EXTRA_LDS")) : 0;  // occupancy experiments only
-  DISPATCH(e, launch_rollout<TL>(e, ds, n_steps, interval, use_vis, write_obs, sb, extra_lds, rec, e->stream, 0, e->n_envs));
-  HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipEventRecord(e->ev1[evi], e->stream));
-  e->hl.ring_lane[e->hl.n_launches % MuavtaEnv::HandleLevel::RING] = (unsigned char)e->lane_id;
-  e->hl.ring_no[e->hl.n_launches % MuavtaEnv::HandleLevel::RING] = e->n_rollouts;
-  e->hl.n_launches++;
-  e->n_rollouts++;
-  e->timing_stale = false;
-  if (slot >= 0) { int rc = seeding_consumed(e, slot); if (rc) return rc; }
-  e->did_reset = true;
-  e->host_valid = false;
-  return MUAVTA_OK;
-}
-int muavta_rollout(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, int32_t interval, int32_t use_vis, int32_t write_obs) {
-  return rollout_impl(e, seeds, n_steps, interval, use_vis, write_obs, nullptr);
-}
-int muavta_rollout_record(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, int32_t interval, int32_t use_vis, int32_t write_obs, const MuavtaRecord* rec) {
-  int dt, da;
-  bool bad = !e || !rec;
-  if (!bad && rec->kind >= 0)
-    bad = token_dims(rec->kind, &dt, &da) || rec->max_tasks < 1 || rec->max_agents < 1 || rec->max_tasks > 4096 || rec->max_agents > 4096 || !rec->task_feats ||
-          !rec->task_mask || !rec->task_ids || !rec->agent_feats || !rec->agent_mask || !rec->agent_ids || !rec->edge_valid || !rec->s_wps;
-  const bool any_obs = !bad && (rec->obs_tasks || rec->obs_legal || rec->obs_pad || rec->obs_agents || rec->obs_flags || rec->obs_reward || rec->obs_done);
-  if (any_obs)  // all seven or none, and only with per-step observations switched on
-    bad = !(rec->obs_tasks && rec->obs_legal && rec->obs_pad && rec->obs_agents && rec->obs_flags && rec->obs_reward && rec->obs_done) || !write_obs;
-  if (!bad && rec->kind < 0 && !any_obs) bad = true;  // nothing to record
-  if (bad) {
-    if (e) e->err = "muavta_rollout_record: bad argument";
-    return MUAVTA_E_ARG;
-  }
-  if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) {  // the recording kernels carry the Hungarian-family planners only
-    e->err = e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR
-                 ? "muavta_rollout_record: not available with the MLP-Pair allocator (set_allocator back to a Hungarian mode)"
-                 : "muavta_rollout_record: not available with the Cap-Greedy / PI allocators (set_allocator back to a Hungarian mode)";
-    return MUAVTA_E_ARG;
-  }
-  return rollout_impl(e, seeds, n_steps, interval, use_vis, write_obs, rec);  // (pre-fills obs_done once the lane is chosen)
-}
-
-// ---- sub-batches ---------------------------------------------------------------------------------------------------------
-int muavta_set_parts(MuavtaEnv* e, int32_t n_parts) {
-  if (!e || n_parts < 0 || n_parts > MuavtaEnv::MAX_PARTS || n_parts > e->n_envs) { if (e) e->err = "muavta_set_parts: 0 .. 8 parts, at most one per env"; return MUAVTA_E_ARG; }
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);  // whatever the old parts hold is ordered in front of the main stream
-  if (n_parts == 1) n_parts = 0;
-  for (int p = 0; p < n_parts; p++) {
-    if (!e->part_stream[p]) {  // (not among the MUAVTA_EAGER_PART_STREAMS created by muavta_create)
-      HIPCHK(e, hipStreamCreateWithFlags(&e->part_stream[p], hipStreamNonBlocking));
-      HIPCHK(e, hipEventCreateWithFlags(&e->part_ev[p], hipEventDisableTiming));
-      HIPCHK(e, hipEventRecord(e->part_ev[p], e->part_stream[p]));
-    }
-    e->part_busy[p] = false; e->part_fork_needed[p] = true;
-  }
-  if (n_parts && !e->d_part_agent) {
-    HIPCHK(e, hipMalloc((void**)&e->d_part_agent, (size_t)e->n_envs * e->A * sizeof(int32_t)));
-    HIPCHK(e, hipMalloc((void**)&e->d_part_index, (size_t)e->n_envs * e->A * sizeof(int32_t)));
-  }
-  e->n_parts = n_parts;
-  if (e->hl.twin) return muavta_set_parts(e->hl.twin, n_parts);
-  return MUAVTA_OK;
-}
-int muavta_part_range(const MuavtaEnv* e, int32_t part, int32_t* first, int32_t* count) {
-  if (!e || !first || !count || part < 0 || part >= (e->n_parts > 0 ? e->n_parts : 1)) return MUAVTA_E_ARG;
-  int f, c;
-  part_range(e, part, &f, &c);
-  *first = f; *count = c;
-  return MUAVTA_OK;
-}
-int muavta_rollout_part(MuavtaEnv* e, int32_t part, int32_t n_steps, int32_t interval, int32_t use_vis, int32_t write_obs) {
-  { int rc = check_part(e, part, "muavta_rollout_part"); if (rc) return rc; }
-  if (n_steps < 0) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  { int rc = fork_part(e, part); if (rc) return rc; }
-  int first, count;
-  part_range(e, part, &first, &count);
-  DISPATCH(e, launch_rollout<TL>(e, nullptr, n_steps, interval, use_vis, write_obs, nullptr, 0, nullptr, e->part_stream[part], first, count));
-  HIPCHK(e, hipGetLastError());
-  e->timing_stale = true;  // (part launches carry no event pair: muavta_last_kernel_ms / _history refuse until the next whole-batch rollout)
-  e->host_valid = false;
-  return MUAVTA_OK;
-}
-int muavta_step_part(MuavtaEnv* e, int32_t part, const int32_t* act_agent, const int32_t* act_index) {
-  { int rc = check_part(e, part, "muavta_step_part"); if (rc) return rc; }
-  if (e->d_rel) { e->err = "muavta_step_part: the release log is a whole-batch facility (muavta_set_release_log off)"; return MUAVTA_E_STATE; }
-  int first, count;
-  part_range(e, part, &first, &count);
-  if (act_agent && act_index) {
-    for (int n = 0; n < count; n++)
-      for (int k = 0; k < e->A; k++) {
-        const int a = act_agent[(size_t)n * e->A + k];
-        if (a < 0) break;
-        if (a >= e->P.n_agents) { e->err = "muavta_step_part: agent id out of range"; return MUAVTA_E_ARG; }
-      }
-  } else if (act_agent || act_index) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  { int rc = fork_part(e, part); if (rc) return rc; }
-  hipStream_t st = e->part_stream[part];
-  const int32_t *da = nullptr, *di = nullptr;
-  if (act_agent) {  // rows first .. first + count of the staging pair; NULL: the actions muavta_allocate_part staged in the blob
-    const size_t off = (size_t)first * e->A, bytes = (size_t)count * e->A * sizeof(int32_t);
-    HIPCHK(e, hipMemcpyAsync(e->d_part_agent + off, act_agent, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipMemcpyAsync(e->d_part_index + off, act_index, bytes, hipMemcpyHostToDevice, st));
-    da = e->d_part_agent; di = e->d_part_index;
-  }
-  DISPATCH(e, hipLaunchKernelGGL(k_step<TL>, dim3(count), dim3(WG), 0, st, (const DevCtx*)e->d_ctx, da, di, e->A, (double*)nullptr, first));
-  HIPCHK(e, hipGetLastError());
-  e->host_valid = false;
-  return MUAVTA_OK;
-}
-int muavta_allocate_part(MuavtaEnv* e, int32_t part, int32_t interval, int32_t use_vis, int32_t* act_agent, int32_t* act_index) {
-  { int rc = check_part(e, part, "muavta_allocate_part"); if (rc) return rc; }
-  DeviceScope scope_(e->device);
-  { int rc = fork_part(e, part); if (rc) return rc; }
-  int first, count;
-  part_range(e, part, &first, &count);
-  hipStream_t st = e->part_stream[part];
-  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR)
-    DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, false, true>), dim3(count), dim3(WG), Lds<TL>::bytes() + SCORED_EXTRA_LDS, st, (const DevCtx*)e->d_ctx, interval, use_vis,
-                                   e->alloc_mode, e->d_part_agent, e->d_part_index, e->A, first))
-  else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY)
-    DISPATCH(e, hipLaunchKernelGGL((k_allocate<TL, true>), dim3(count), dim3(WG), Lds<TL>::bytes(), st, (const DevCtx*)e->d_ctx, interval, use_vis,
-                                   e->alloc_mode, e->d_part_agent, e->d_part_index, e->A, first))
-  else
-    DISPATCH(e, hipLaunchKernelGGL(k_allocate<TL>, dim3(count), dim3(WG), Lds<TL>::bytes(), st, (const DevCtx*)e->d_ctx, interval, use_vis, e->alloc_mode,
-                                   e->d_part_agent, e->d_part_index, e->A, first));
-  HIPCHK(e, hipGetLastError());
-  e->host_valid = false;
-  if (act_agent && act_index) {
-    const size_t off = (size_t)first * e->A, bytes = (size_t)count * e->A * sizeof(int32_t);
-    HIPCHK(e, hipMemcpyAsync(act_agent, e->d_part_agent + off, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipMemcpyAsync(act_index, e->d_part_index + off, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-  }
-  return MUAVTA_OK;
-}
-int muavta_observe_part(MuavtaEnv* e, int32_t part, float* tasks, uint64_t* legal, uint8_t* pad, float* agents, float* flags, double* reward, uint8_t* done) {
-  { int rc = check_part(e, part, "muavta_observe_part"); if (rc) return rc; }
-  DeviceScope scope_(e->device);
-  { int rc = fork_part(e, part); if (rc) return rc; }
-  int first, count;
-  part_range(e, part, &first, &count);
-  hipStream_t st = e->part_stream[part];
-  const size_t F = (size_t)first, C = (size_t)count, mt = (size_t)e->P.max_tasks, nA = (size_t)e->P.n_agents, kw = (mt + 63) / 64;
-  if (tasks) HIPCHK(e, hipMemcpyAsync(tasks, e->O.tasks + F * mt * 21, C * mt * 21 * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (legal) HIPCHK(e, hipMemcpyAsync(legal, e->O.legal + F * nA * kw, C * nA * kw * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  if (pad) HIPCHK(e, hipMemcpyAsync(pad, e->O.pad + F * mt, C * mt, hipMemcpyDeviceToHost, st));
-  if (agents) HIPCHK(e, hipMemcpyAsync(agents, e->O.agents + F * nA * 9, C * nA * 9 * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (flags) HIPCHK(e, hipMemcpyAsync(flags, e->O.flags + F * 5, C * 5 * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (reward) HIPCHK(e, hipMemcpyAsync(reward, e->O.reward + F, C * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (done) HIPCHK(e, hipMemcpyAsync(done, e->O.done + F, C, hipMemcpyDeviceToHost, st));
-  HIPCHK(e, hipStreamSynchronize(st));
-  return MUAVTA_OK;
-}
-int muavta_wait_part(MuavtaEnv* e, int32_t part) {  // part < 0: every part
-  if (!e || part >= e->n_parts) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  for (int p = 0; p < e->n_parts; p++)
-    if (part < 0 || p == part) HIPCHK(e, hipStreamSynchronize(e->part_stream[p]));
-  return MUAVTA_OK;
-}
-
-#ifdef MUAVTA_DIAG_TIMES
-int muavta_diag_times(MuavtaEnv* e, uint32_t* out, int32_t n) {  // diagnostic build only: [3][n] start, end (10 ns units), hw ids
-  DeviceScope scope_(e->device);
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  for (int k = 0; k < 3; k++)
-    HIPCHK(e, hipMemcpy(out + (size_t)k * n, e->d_pace + (1u << 19) + 65536u * k, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return MUAVTA_OK;
-}
-#endif
-#ifdef MUAVTA_PROF
-int muavta_prof_target(int env) { return hipMemcpyToSymbol(HIP_SYMBOL(g_prof_target), &env, sizeof(env)) == hipSuccess ? MUAVTA_OK : MUAVTA_E_HIP; }  // diagnostic build only
-int muavta_prof_read(unsigned long long* out, int reset) {  // diagnostic build only
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), PROF_N * sizeof(unsigned long long)) != hipSuccess) return MUAVTA_E_HIP;
-  if (reset) { unsigned long long z[PROF_N] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)) != hipSuccess) return MUAVTA_E_HIP; }
-  return MUAVTA_OK;
-}
-#endif
-
-int muavta_set_allocator(MuavtaEnv* e, int32_t mode) {
-  if (!e || (mode < MUAVTA_ALLOC_HUNGARIAN || mode > MUAVTA_ALLOC_MLP_PAIR)) { if (e) e->err = "unknown allocator mode"; return MUAVTA_E_ARG; }
-  if (mode == MUAVTA_ALLOC_MLP_PAIR && !e->hl.pol_set) {
-    e->err = "muavta_set_allocator: MUAVTA_ALLOC_MLP_PAIR needs a policy (muavta_set_pair_policy first)";
-    return MUAVTA_E_STATE;
-  }
-  e->alloc_mode = mode;
-  if (e->hl.twin) e->hl.twin->alloc_mode = mode;
-  return MUAVTA_OK;
-}
-
-// ---- the learned MLP-Pair hybrid (sim/policy.inc) ---------------------------------------------------------------------------------
-int muavta_set_pair_policy(MuavtaEnv* e, const MuavtaPairMlp* spec) {
-  if (!e) return MUAVTA_E_ARG;
-  // what the handle holds now: put back if the new policy does not reach BOTH lanes (the handle-level record must never say "set"
-  // while a lane's context holds no, or another, policy)
-  std::vector<float> old_w = e->hl.pol_w;
-  const int old_raw = e->hl.pol_raw;
-  const float old_clamp = e->hl.pol_clamp;
-  const bool old_set = e->hl.pol_set;
-  if (!spec) {  // clear
-    if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) {
-      e->err = "muavta_set_pair_policy: the MLP-Pair allocator is selected; muavta_set_allocator to another mode before clearing its policy";
-      return MUAVTA_E_STATE;
-    }
-    e->hl.pol_set = false;
-    e->hl.pol_w.clear();
-  } else {
-    if (spec->hidden != PW_HID || (spec->raw_features != 0 && spec->raw_features != 1) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 || !spec->w2 ||
-        !spec->b2 || !(spec->score_clamp == spec->score_clamp)) {
-      e->err = "muavta_set_pair_policy: bad spec (hidden must be 128, raw_features 0 or 1, six non-null arrays, score_clamp a number)";
-      return MUAVTA_E_ARG;
-    }
-    const int k0 = spec->raw_features ? 20 : 25;
-    std::vector<float> w((size_t)PW_FLOATS, 0.f);
-    for (int n = 0; n < PW_HID; n++)
-      for (int k = 0; k < k0; k++) w[PW_W0 + (size_t)k * PW_HID + n] = spec->w0[(size_t)n * k0 + k];  // k-major on the device
-    memcpy(&w[PW_B0], spec->b0, PW_HID * sizeof(float));
-    for (int n = 0; n < PW_HID; n++)
-      for (int k = 0; k < PW_HID; k++) w[PW_W1 + ((size_t)(n / 4) * PW_HID + k) * 4 + n % 4] = spec->w1[(size_t)n * PW_HID + k];  // four outputs interleaved
-    memcpy(&w[PW_B1], spec->b1, PW_HID * sizeof(float));
-    memcpy(&w[PW_W2], spec->w2, PW_HID * sizeof(float));
-    w[PW_B2] = spec->b2[0];
-    e->hl.pol_w.swap(w);
-    e->hl.pol_raw = spec->raw_features; e->hl.pol_clamp = spec->score_clamp; e->hl.pol_set = true;
-  }
-  int rc = push_policy(e, e->hl);
-  if (rc == MUAVTA_OK && e->hl.twin) { rc = push_policy(e->hl.twin, e->hl); if (rc) e->err = e->hl.twin->err; }
-  if (rc == MUAVTA_OK) return MUAVTA_OK;
-  const std::string why = e->err;
-  e->hl.pol_w.swap(old_w); e->hl.pol_raw = old_raw; e->hl.pol_clamp = old_clamp; e->hl.pol_set = old_set;
-  int back = push_policy(e, e->hl);
-  if (back == MUAVTA_OK && e->hl.twin) back = push_policy(e->hl.twin, e->hl);
-  if (back != MUAVTA_OK) {  // not even the previous policy could be put back: no policy, and no mode that needs one
-    e->hl.pol_set = false;
-    e->hl.pol_w.clear();
-    if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) { e->alloc_mode = MUAVTA_ALLOC_HUNGARIAN; if (e->hl.twin) e->hl.twin->alloc_mode = MUAVTA_ALLOC_HUNGARIAN; }
-    e->err = "muavta_set_pair_policy failed (" + why + ") and the previous policy could not be restored: the handle has no policy now and runs the Hungarian allocator";
-    return rc;
-  }
-  e->err = "muavta_set_pair_policy failed, the previous policy is kept: " + why;
-  return rc;
-}
-int muavta_pair_scores_device(MuavtaEnv* e, float* scores, float* logits) {
-  if (!e) return MUAVTA_E_ARG;
-  if (!e->hl.pol_set) { e->err = "muavta_pair_scores: no policy (muavta_set_pair_policy first)"; return MUAVTA_E_STATE; }
-  if (!e->did_reset) { e->err = "muavta_pair_scores before reset"; return MUAVTA_E_STATE; }
-  if (!scores && !logits) return MUAVTA_OK;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  DISPATCH(e, hipLaunchKernelGGL(k_pair_scores<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits));
-  HIPCHK(e, hipGetLastError());
-  return MUAVTA_OK;
-}
-int muavta_pair_scores(MuavtaEnv* e, float* scores, float* logits) {
-  if (!e) return MUAVTA_E_ARG;
-  if (!e->hl.pol_set) { e->err = "muavta_pair_scores: no policy (muavta_set_pair_policy first)"; return MUAVTA_E_STATE; }
-  if (!e->did_reset) { e->err = "muavta_pair_scores before reset"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  const size_t one = (size_t)e->n_envs * PS_MA * PS_MT * sizeof(float);
-  if (2 * one > e->tok_bytes) {  // (shares the staging buffer of muavta_tokens' host variant)
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (e->d_tok) hipFree(e->d_tok);
-    e->d_tok = nullptr; e->tok_bytes = 0;
-    HIPCHK(e, hipMalloc(&e->d_tok, 2 * one));
-    e->tok_bytes = 2 * one;
-  }
-  float* ds = (float*)e->d_tok;
-  float* dl = (float*)((char*)e->d_tok + one);
-  if (int rc = muavta_pair_scores_device(e, scores ? ds : nullptr, logits ? dl : nullptr)) return rc;
-  if (scores) HIPCHK(e, hipMemcpyAsync(scores, ds, one, hipMemcpyDeviceToHost, e->stream));
-  if (logits) HIPCHK(e, hipMemcpyAsync(logits, dl, one, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-
-int muavta_sync(MuavtaEnv* e) {
-  if (!e) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  if (e->hl.twin) { int rc = muavta_sync(e->hl.twin); if (rc) { e->err = e->hl.twin->err; return rc; } }  // everything queued on the handle: both lanes
-  MAIN_OP(e);
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-
-int muavta_wait_stream(MuavtaEnv* e, void* other_stream) {  // work queued on the handle from now on starts after what `other_stream` holds now
-  if (!e) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  hipEvent_t ev = nullptr;
-  HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  hipError_t r = hipEventRecord(ev, (hipStream_t)other_stream);
-  for (MuavtaEnv* L : {e, e->hl.twin}) {  // both lanes
-    if (!L || r != hipSuccess) continue;
-    r = hipStreamWaitEvent(L->stream, ev, 0);
-    // sub-batches: a part's stream is ordered after the main stream's work at its next launch (fork_part), so the wait carries over
-    for (int p = 0; p < L->n_parts; p++) L->part_fork_needed[p] = true;
-  }
-  if (r == hipSuccess && !e->hl.twin) {
-    // no second lane yet: ensure_twin makes one created later wait on the event too.  Events whose work has completed order
-    // nothing any more and are dropped here, so a caller that never gets a second lane keeps only the waits still in flight.
-    auto& pw = e->hl.pending_waits;
-    size_t k = 0;
-    for (hipEvent_t w : pw) { if (hipEventQuery(w) == hipSuccess) hipEventDestroy(w); else pw[k++] = w; }
-    (void)hipGetLastError();
-    pw.resize(k);
-    pw.push_back(ev);
-    ev = nullptr;
-  }
-  if (ev) hipEventDestroy(ev);  // (destruction is deferred by the runtime until the event has completed)
-  if (r != hipSuccess) { e->err = std::string("muavta_wait_stream: ") + hipGetErrorString(r); return MUAVTA_E_HIP; }
-  return MUAVTA_OK;
-}
-
-int muavta_last_kernel_ms(MuavtaEnv* e, float* ms) {
-  if (!e || !ms) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  if (!e->n_rollouts) { e->err = "no rollout launched yet"; return MUAVTA_E_STATE; }
-  if (e->timing_stale) { e->err = "muavta_last_kernel_ms: the last rollout was a muavta_rollout_part launch, which records no event pair"; return MUAVTA_E_STATE; }
-  const int evi = (int)((e->n_rollouts - 1) % MuavtaEnv::EV_RING);
-  HIPCHK(e, hipEventSynchronize(e->ev1[evi]));
-  HIPCHK(e, hipEventElapsedTime(ms, e->ev0[evi], e->ev1[evi]));
-  e->last_ms = *ms;
-  return MUAVTA_OK;
-}
-
-int muavta_kernel_ms_history(MuavtaEnv* e, float* ms, int32_t n) {  // durations of the last n rollout launches, oldest first
-  if (!e || !ms || n < 1 || n > MuavtaEnv::EV_RING) { if (e) e->err = "muavta_kernel_ms_history: 1 <= n <= 64"; return MUAVTA_E_ARG; }
-  if ((unsigned long long)n > e->hl.n_launches) { e->err = "fewer rollouts launched than asked for"; return MUAVTA_E_STATE; }
-  if (e->timing_stale) { e->err = "muavta_kernel_ms_history: the last rollout was a muavta_rollout_part launch, which records no event pair"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  for (int k = 0; k < n; k++) {  // (with two state lanes consecutive launches alternate between the lanes' event rings and may overlap on the device)
-    const unsigned long long h = e->hl.n_launches - (unsigned long long)n + (unsigned long long)k;
-    MuavtaEnv* L = lane_by_id(e, e->hl.ring_lane[h % MuavtaEnv::HandleLevel::RING]);
-    const unsigned long long no = e->hl.ring_no[h % MuavtaEnv::HandleLevel::RING];
-    if (!L || L->n_rollouts - no > (unsigned long long)MuavtaEnv::EV_RING) { e->err = "muavta_kernel_ms_history: that launch's event pair has been reused"; return MUAVTA_E_STATE; }
-    const int evi = (int)(no % MuavtaEnv::EV_RING);
-    HIPCHK(e, hipEventSynchronize(L->ev1[evi]));
-    HIPCHK(e, hipEventElapsedTime(&ms[k], L->ev0[evi], L->ev1[evi]));
-  }
-  e->last_ms = ms[n - 1];
-  return MUAVTA_OK;
-}
-
-int muavta_launch_gaps_ms(MuavtaEnv* e, float* ms, int32_t n) {  // idle time of the handle's stream between the last n rollout launches: n - 1 gaps, oldest first
-  if (!e || !ms || n < 2 || n > MuavtaEnv::EV_RING) { if (e) e->err = "muavta_launch_gaps_ms: 2 <= n <= 64"; return MUAVTA_E_ARG; }
-  if ((unsigned long long)n > e->hl.n_launches) { e->err = "fewer rollouts launched than asked for"; return MUAVTA_E_STATE; }
-  if (e->timing_stale) { e->err = "muavta_launch_gaps_ms: the last rollout was a muavta_rollout_part launch, which records no event pair"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  for (int k = 0; k + 1 < n; k++) {  // end of launch i .. start of launch i + 1 (NEGATIVE when they ran on different lanes and overlapped)
-    const unsigned long long ha = e->hl.n_launches - (unsigned long long)n + (unsigned long long)k, hb = ha + 1;
-    MuavtaEnv* La = lane_by_id(e, e->hl.ring_lane[ha % MuavtaEnv::HandleLevel::RING]);
-    MuavtaEnv* Lb = lane_by_id(e, e->hl.ring_lane[hb % MuavtaEnv::HandleLevel::RING]);
-    const unsigned long long na = e->hl.ring_no[ha % MuavtaEnv::HandleLevel::RING], nb = e->hl.ring_no[hb % MuavtaEnv::HandleLevel::RING];
-    if (!La || !Lb || La->n_rollouts - na > (unsigned long long)MuavtaEnv::EV_RING || Lb->n_rollouts - nb > (unsigned long long)MuavtaEnv::EV_RING) {
-      e->err = "muavta_launch_gaps_ms: an event pair has been reused"; return MUAVTA_E_STATE;
-    }
-    const int a = (int)(na % MuavtaEnv::EV_RING), b = (int)(nb % MuavtaEnv::EV_RING);
-    HIPCHK(e, hipEventSynchronize(Lb->ev0[b]));
-    HIPCHK(e, hipEventSynchronize(La->ev1[a]));
-    if (La == Lb) HIPCHK(e, hipEventElapsedTime(&ms[k], La->ev1[a], Lb->ev0[b]));
-    else {  // events of two streams: elapsed time in either direction, signed
-      float fwd = 0.f;
-      hipError_t r = hipEventElapsedTime(&fwd, La->ev1[a], Lb->ev0[b]);
-      if (r != hipSuccess) { e->err = std::string("hipEventElapsedTime: ") + hipGetErrorString(r); return MUAVTA_E_HIP; }
-      ms[k] = fwd;
-    }
-  }
-  return MUAVTA_OK;
-}
-
-int muavta_last_seed_ms(MuavtaEnv* e, float* ms) {  // the RNG seeding kernel that preceded the last muavta_rollout (0 without seeds)
-  if (!e || !ms) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  *ms = 0.f;
-  if (!e->last_seeded) return MUAVTA_OK;
-  HIPCHK(e, hipEventSynchronize(e->ev_seeded[e->last_seed_slot]));
-  HIPCHK(e, hipEventElapsedTime(ms, e->ev_seed0[e->last_seed_slot], e->ev_seeded[e->last_seed_slot]));
-  return MUAVTA_OK;
-}
-
-int muavta_observe(MuavtaEnv* e, float* tasks, uint64_t* legal, uint8_t* pad, float* agents, float* flags) {
-  if (!e) return MUAVTA_E_ARG;
-  if (!e->did_reset) { e->err = "observe before reset"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  const size_t N = (size_t)e->n_envs, mt = (size_t)e->P.max_tasks, nA = (size_t)e->P.n_agents;
-  if (tasks) HIPCHK(e, hipMemcpyAsync(tasks, e->O.tasks, N * mt * 21 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (legal) HIPCHK(e, hipMemcpyAsync(legal, e->O.legal, N * nA * ((mt + 63) / 64) * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
-  if (pad) HIPCHK(e, hipMemcpyAsync(pad, e->O.pad, N * mt, hipMemcpyDeviceToHost, e->stream));
-  if (agents) HIPCHK(e, hipMemcpyAsync(agents, e->O.agents, N * nA * 9 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (flags) HIPCHK(e, hipMemcpyAsync(flags, e->O.flags, N * 5 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-
-// ---- token builders --------------------------------------------------------------------------
-static int token_dims(int kind, int* dt, int* da) {
-  if (kind == MUAVTA_TOK_PAIR) { *dt = 13; *da = 12; }
-  else if (kind == MUAVTA_TOK_PAIR_RAW) { *dt = 9; *da = 11; }
-  else if (kind == MUAVTA_TOK_ESCORT) { *dt = 22; *da = 16; }
-  else return MUAVTA_E_ARG;
-  return MUAVTA_OK;
-}
-int muavta_tokens_device(MuavtaEnv* e, int32_t kind, int32_t max_tasks, int32_t max_agents, float* task_feats, uint8_t* task_mask,
-                         int32_t* task_ids, float* agent_feats, uint8_t* agent_mask, int32_t* agent_ids, float* edge_valid, int32_t* n_urgent,
-                         float* expert_mask, int32_t* replanned) {
-  int dt, da;
-  if (!e || token_dims(kind, &dt, &da) || max_tasks < 1 || max_agents < 1 || max_tasks > 4096 || max_agents > 4096 || !task_feats || !task_mask ||
-      !task_ids || !agent_feats || !agent_mask || !agent_ids || !edge_valid) { if (e) e->err = "muavta_tokens: bad argument"; return MUAVTA_E_ARG; }
-  if (!e->did_reset) { e->err = "tokens before reset"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  DISPATCH(e, launch_tokens<TL>(e, kind, max_tasks, max_agents, task_feats, task_mask, task_ids, agent_feats, agent_mask, agent_ids, edge_valid, n_urgent, expert_mask, replanned));
-  HIPCHK(e, hipGetLastError());
-  return MUAVTA_OK;
-}
-int muavta_tokens(MuavtaEnv* e, int32_t kind, int32_t max_tasks, int32_t max_agents, float* task_feats, uint8_t* task_mask,
-                  int32_t* task_ids, float* agent_feats, uint8_t* agent_mask, int32_t* agent_ids, float* edge_valid, int32_t* n_urgent,
-                  float* expert_mask, int32_t* replanned) {
-  int dt, da;
-  if (!e || token_dims(kind, &dt, &da) || max_tasks < 1 || max_agents < 1) { if (e) e->err = "muavta_tokens: bad argument"; return MUAVTA_E_ARG; }
-  DeviceScope scope_(e->device);
-  const size_t N = (size_t)e->n_envs, MT = (size_t)max_tasks, MA = (size_t)max_agents;
-  const size_t sz[10] = {N * MT * dt * 4, N * MT, N * MT * 4, N * MA * da * 4, N * MA, N * MA * 4, N * MA * MT * 4, N * 4, N * MA * MT * 4, N * 4};
-  size_t off[11] = {0};
-  for (int i = 0; i < 10; i++) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
-  if (off[10] > e->tok_bytes) {
-    if (e->d_tok) hipFree(e->d_tok);
-    e->d_tok = nullptr; e->tok_bytes = 0;
-    HIPCHK(e, hipMalloc(&e->d_tok, off[10]));
-    e->tok_bytes = off[10];
-  }
-  char* b = (char*)e->d_tok;
-  int rc = muavta_tokens_device(e, kind, max_tasks, max_agents, (float*)(b + off[0]), (uint8_t*)(b + off[1]), (int32_t*)(b + off[2]),
-                                (float*)(b + off[3]), (uint8_t*)(b + off[4]), (int32_t*)(b + off[5]), (float*)(b + off[6]), (int32_t*)(b + off[7]),
-                                expert_mask ? (float*)(b + off[8]) : nullptr, replanned ? (int32_t*)(b + off[9]) : nullptr);
-  if (rc) return rc;
-  void* host[10] = {task_feats, task_mask, task_ids, agent_feats, agent_mask, agent_ids, edge_valid, n_urgent, expert_mask, replanned};
-  for (int i = 0; i < 10; i++)
-    if (host[i]) HIPCHK(e, hipMemcpyAsync(host[i], b + off[i], sz[i], hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-
-int muavta_context_device(MuavtaEnv* e, int32_t kind, int32_t max_tasks, float* context) {
-  if (!e || !context || (kind != MUAVTA_TOK_PAIR && kind != MUAVTA_TOK_PAIR_RAW) || max_tasks < 1 || max_tasks > 4096) {
-    if (e) e->err = "muavta_context: kind MUAVTA_TOK_PAIR (8 floats per env) or MUAVTA_TOK_PAIR_RAW (1), max_tasks >= 1"; return MUAVTA_E_ARG;
-  }
-  if (!e->did_reset) { e->err = "context before reset"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  DISPATCH(e, hipLaunchKernelGGL(k_context<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, (int)(kind == MUAVTA_TOK_PAIR_RAW), max_tasks, context));
-  HIPCHK(e, hipGetLastError());
-  return MUAVTA_OK;
-}
-int muavta_context(MuavtaEnv* e, int32_t kind, int32_t max_tasks, float* context) {
-  if (!e || !context) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  const size_t bytes = (size_t)e->n_envs * (kind == MUAVTA_TOK_PAIR_RAW ? 1 : 8) * sizeof(float);
-  if (bytes > e->tok_bytes) {  // (shares the staging buffer of muavta_tokens' host variant)
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (e->d_tok) hipFree(e->d_tok);
-    e->d_tok = nullptr; e->tok_bytes = 0;
-    HIPCHK(e, hipMalloc(&e->d_tok, bytes));
-    e->tok_bytes = bytes;
-  }
-  if (int rc = muavta_context_device(e, kind, max_tasks, (float*)e->d_tok)) return rc;
-  HIPCHK(e, hipMemcpyAsync(context, e->d_tok, bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-
-int muavta_call(MuavtaEnv* e, int32_t env_index, int32_t op, const int32_t* iargs, double darg, int32_t* out) {
-  if (!e || !out || op < 0 || op >= MUAVTA_OP_COUNT_ || env_index < 0 || env_index >= e->n_envs) { if (e) e->err = "muavta_call: bad argument"; return MUAVTA_E_ARG; }
-  if (!e->did_reset) { e->err = "muavta_call before reset"; return MUAVTA_E_STATE; }
-  CallArgs a;
-  memset(&a, 0, sizeof(a));
-  a.op = op; a.env = env_index; a.d = darg;
-  if (iargs) memcpy(a.i, iargs, sizeof(a.i));
-  const bool has_agent = op != MUAVTA_OP_SYNC_ESCORTS && op != MUAVTA_OP_RETIRE_ESCORT;
-  if (has_agent && (a.i[0] < 0 || a.i[0] >= e->P.n_agents)) { e->err = "muavta_call: agent id out of range"; return MUAVTA_E_ARG; }
-  if (op == MUAVTA_OP_SET_QUEUE && (a.i[1] < 0 || a.i[1] > 6)) { e->err = "muavta_call(SET_QUEUE): at most 6 tasks"; return MUAVTA_E_ARG; }
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  if (!e->d_call_out) HIPCHK(e, hipMalloc((void**)&e->d_call_out, MUAVTA_CALL_OUT * sizeof(int32_t)));
-  DISPATCH(e, hipLaunchKernelGGL(k_call<TL>, dim3(1), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, a, e->d_call_out));
-  HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipMemcpyAsync(out, e->d_call_out, MUAVTA_CALL_OUT * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  e->host_valid = false;
-  return MUAVTA_OK;
-}
-
-// ---- RCCL, loaded on first use --------------------------------------------------------------------------------
-namespace {
-struct Rccl {
-  void* lib = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-  const char* (*GetErrorString)(ncclResult_t) = nullptr;
-  std::string err;
-};
-Rccl* rccl() {
-  static Rccl R;
-  if (R.lib || !R.err.empty()) return &R;
-  const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-  for (const char* n : names) if ((R.lib = dlopen(n, RTLD_NOW | RTLD_NOLOAD))) break;   // a copy already in the process (PyTorch's)
-  if (!R.lib) for (const char* n : names) if ((R.lib = dlopen(n, RTLD_NOW | RTLD_LOCAL))) break;
-  if (!R.lib) { R.err = std::string("librccl not found: ") + dlerror(); return &R; }
-  *(void**)&R.GetUniqueId = dlsym(R.lib, "ncclGetUniqueId");
-  *(void**)&R.CommInitRank = dlsym(R.lib, "ncclCommInitRank");
-  *(void**)&R.CommDestroy = dlsym(R.lib, "ncclCommDestroy");
-  *(void**)&R.AllReduce = dlsym(R.lib, "ncclAllReduce");
-  *(void**)&R.AllGather = dlsym(R.lib, "ncclAllGather");
-  *(void**)&R.GetErrorString = dlsym(R.lib, "ncclGetErrorString");
-  if (!R.GetUniqueId || !R.CommInitRank || !R.CommDestroy || !R.AllReduce || !R.AllGather || !R.GetErrorString) { R.err = "librccl lacks an expected symbol"; R.lib = nullptr; }
-  return &R;
-}
-}  // namespace
-#define NCCLCHK(env, expr)                                                                        \
-  do {                                                                                            \
-    ncclResult_t r_ = (expr);                                                                     \
-    if (r_ != ncclSuccess) { (env)->err = std::string(#expr) + ": " + rccl()->GetErrorString(r_); return MUAVTA_E_HIP; } \
-  } while (0)
-
-int muavta_comm_uid(uint8_t* uid) {
-  if (!uid) return MUAVTA_E_ARG;
-  Rccl* R = rccl();
-  if (!R->lib) { g_create_error = R->err; return MUAVTA_E_NO_DEVICE; }
-  static_assert(sizeof(ncclUniqueId) == MUAVTA_COMM_UID_BYTES, "RCCL unique id size");
-  ncclUniqueId id;
-  ncclResult_t r = R->GetUniqueId(&id);
-  if (r != ncclSuccess) { g_create_error = std::string("ncclGetUniqueId: ") + R->GetErrorString(r); return MUAVTA_E_HIP; }
-  memcpy(uid, &id, sizeof(id));
-  return MUAVTA_OK;
-}
-int muavta_comm_init(MuavtaEnv* e, int32_t rank, int32_t n_ranks, const uint8_t* uid) {
-  if (!e || !uid || n_ranks < 1 || rank < 0 || rank >= n_ranks) { if (e) e->err = "muavta_comm_init: bad arguments"; return MUAVTA_E_ARG; }
-  if (e->comm) { e->err = "muavta_comm_init: this handle already has a communicator"; return MUAVTA_E_STATE; }
-  Rccl* R = rccl();
-  if (!R->lib) { e->err = R->err; return MUAVTA_E_NO_DEVICE; }
-  DeviceScope scope_(e->device);
-  ncclUniqueId id;
-  memcpy(&id, uid, sizeof(id));
-  // staging first: a failure below must not leave a communicator behind that has nowhere to stage (a retry would be refused
-  // as "already has a communicator" and the next all-reduce would touch a null buffer)
-  void* staging = nullptr;
-  HIPCHK(e, hipMalloc(&staging, (size_t)(64 + 64 * n_ranks + 128) * 8));
-  ncclComm_t comm = nullptr;
-  const ncclResult_t r = R->CommInitRank(&comm, n_ranks, id, rank);
-  if (r != ncclSuccess) {
-    hipFree(staging);
-    e->err = std::string("ncclCommInitRank: ") + R->GetErrorString(r);
-    return MUAVTA_E_HIP;
-  }
-  e->comm = comm; e->d_comm = staging;
-  e->comm_rank = rank; e->comm_ranks = n_ranks;
-  return MUAVTA_OK;
-}
-int muavta_allreduce_metrics(MuavtaEnv* e, const double* f_partials, int32_t nf, const int64_t* counters, int32_t nc, double* f_total, int64_t* c_total) {
-  if (!e || nf < 0 || nc < 0 || nf > 64 || nc > 64 || (nf && (!f_partials || !f_total)) || (nc && (!counters || !c_total))) { if (e) e->err = "muavta_allreduce_metrics: bad arguments"; return MUAVTA_E_ARG; }
-  if (!e->comm) { e->err = "muavta_allreduce_metrics before muavta_comm_init"; return MUAVTA_E_STATE; }
-  Rccl* R = rccl();
-  DeviceScope scope_(e->device);
-  const int n = e->comm_ranks;
-  double* fs = (double*)e->d_comm; double* fr = fs + 64;
-  int64_t* cs = (int64_t*)(fr + (size_t)64 * n); int64_t* cr = cs + 64;
-  if (nf) {
-    HIPCHK(e, hipMemcpyAsync(fs, f_partials, (size_t)nf * 8, hipMemcpyHostToDevice, e->stream));
-    NCCLCHK(e, R->AllGather(fs, fr, (size_t)nf, ncclDouble, e->comm, e->stream));
-  }
-  if (nc) {
-    HIPCHK(e, hipMemcpyAsync(cs, counters, (size_t)nc * 8, hipMemcpyHostToDevice, e->stream));
-    NCCLCHK(e, R->AllReduce(cs, cr, (size_t)nc, ncclInt64, ncclSum, e->comm, e->stream));
-  }
-  std::vector<double> gathered((size_t)nf * n);
-  if (nf) HIPCHK(e, hipMemcpyAsync(gathered.data(), fr, gathered.size() * 8, hipMemcpyDeviceToHost, e->stream));
-  if (nc) HIPCHK(e, hipMemcpyAsync(c_total, cr, (size_t)nc * 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  for (int k = 0; k < nf; k++) {  // rank order: the same bits on every rank, whatever the ring order
-    double s = 0.0;
-    for (int r = 0; r < n; r++) s += gathered[(size_t)r * nf + k];
-    f_total[k] = s;
-  }
-  return MUAVTA_OK;
-}
-int muavta_comm_destroy(MuavtaEnv* e) {
-  if (!e) return MUAVTA_E_ARG;
-  if (e->comm) {
-    DeviceScope scope_(e->device);
-    hipStreamSynchronize(e->stream);
-    rccl()->CommDestroy(e->comm);
-    e->comm = nullptr;
-    hipFree(e->d_comm);
-    e->d_comm = nullptr;
-  }
-  return MUAVTA_OK;
-}
-
-int muavta_set_release_log(MuavtaEnv* e, int32_t enable) {
-  if (!e) return MUAVTA_E_ARG;
-  if (e->hl.twin) { int rc = muavta_set_release_log(e->hl.twin, enable); if (rc) { e->err = e->hl.twin->err; return rc; } }
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  if (enable && !e->d_rel) {
-    const size_t bytes = (size_t)e->n_envs * (1 + MUAVTA_REL_ROW * e->T) * sizeof(double);
-    HIPCHK(e, hipMalloc((void**)&e->d_rel, bytes));
-    HIPCHK(e, hipMemset(e->d_rel, 0, bytes));
-  } else if (!enable && e->d_rel) {
-    hipFree(e->d_rel);
-    e->d_rel = nullptr;
-  }
-  return MUAVTA_OK;
-}
-
-int muavta_refresh_observation(MuavtaEnv* e) {  // rebuild the obs tensors from the current state (after muavta_set)
-  if (!e) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  DISPATCH(e, hipLaunchKernelGGL(k_observe<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx));
-  HIPCHK(e, hipGetLastError());
-  e->host_valid = false;  // (the kernel refreshes the derived initTime / doneTime rows of the HBM record)
-  return MUAVTA_OK;
-}
-
-int muavta_step_result(MuavtaEnv* e, double* reward, uint8_t* done) {
-  if (!e) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  if (reward) HIPCHK(e, hipMemcpyAsync(reward, e->O.reward, (size_t)e->n_envs * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  if (done) HIPCHK(e, hipMemcpyAsync(done, e->O.done, (size_t)e->n_envs, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-
-int muavta_metrics(MuavtaEnv* e, double* out) {
-  if (!e || !out) return MUAVTA_E_ARG;
-  if (!e->did_reset) { e->err = "metrics before reset"; return MUAVTA_E_STATE; }
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  DISPATCH(e, hipLaunchKernelGGL(k_metrics<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, e->d_metrics));
-  HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipMemcpyAsync(out, e->d_metrics, (size_t)e->n_envs * MUAVTA_N_METRICS * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  int rc = sync_host(e);
-  if (rc) return rc;
-  DISPATCH(e, rc = check_errors<TL>(e));
-  return rc;
-}
-
-int muavta_get(MuavtaEnv* e, MuavtaField field, void* dst, size_t bytes) {
-  if (!e || !dst) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  if (field == MUAVTA_F_RELEASE_LOG) {
-    const size_t want = (size_t)e->n_envs * (1 + MUAVTA_REL_ROW * e->T) * sizeof(double);
-    if (!e->d_rel) { e->err = "release log is off (muavta_set_release_log)"; return MUAVTA_E_STATE; }
-    if (bytes != want) { e->err = "muavta_get(RELEASE_LOG): wrong size"; return MUAVTA_E_ARG; }
-    MAIN_OP(e);
-    HIPCHK(e, hipMemcpyAsync(dst, e->d_rel, want, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return MUAVTA_OK;
-  }
-  int rc = sync_host(e);
-  if (rc) return rc;
-  DISPATCH(e, rc = gather<TL>(e, field, dst, bytes, false));
-  return rc;
-}
-
-int muavta_set(MuavtaEnv* e, MuavtaField field, const void* src, size_t bytes) {
-  if (!e || !src) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  int rc = sync_host(e);
-  if (rc) return rc;
-  DISPATCH(e, rc = gather<TL>(e, field, const_cast<void*>(src), bytes, true));
-  if (rc) return rc;
-  DISPATCH(e, forget_obs_rows<TL>(e));
-  HIPCHK(e, hipMemcpyAsync(e->blobs, e->host_blobs.data(), e->host_blobs.size(), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(e, hipMemcpyAsync(e->cold, e->host_cold.data(), e->host_cold.size(), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-
-int muavta_get_state(MuavtaEnv* e, void* dst, size_t bytes) {  // [N x EnvState | N x EnvCold]
-  if (!e || !dst || bytes != (size_t)e->n_envs * (e->state_bytes + e->cold_bytes)) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  HIPCHK(e, hipMemcpyAsync(dst, e->blobs, (size_t)e->n_envs * e->state_bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipMemcpyAsync((char*)dst + (size_t)e->n_envs * e->state_bytes, e->cold, (size_t)e->n_envs * e->cold_bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-int muavta_set_state(MuavtaEnv* e, const void* src, size_t bytes) {
-  if (!e || !src || bytes != (size_t)e->n_envs * (e->state_bytes + e->cold_bytes)) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  e->host_blobs.assign((const unsigned char*)src, (const unsigned char*)src + (size_t)e->n_envs * e->state_bytes);
-  DISPATCH(e, forget_obs_rows<TL>(e));  // (the observation buffer belongs to another moment than the restored state)
-  HIPCHK(e, hipMemcpyAsync(e->blobs, e->host_blobs.data(), (size_t)e->n_envs * e->state_bytes, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(e, hipMemcpyAsync(e->cold, (const char*)src + (size_t)e->n_envs * e->state_bytes, (size_t)e->n_envs * e->cold_bytes, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  e->host_valid = false;
-  e->did_reset = true;
-  return MUAVTA_OK;
-}
-int muavta_get_rng(MuavtaEnv* e, void* dst, size_t bytes) {  // raw MT tapes, for checkpoint/resume next to get_state
-  size_t need = e ? (size_t)e->n_envs * MUAVTA_RNG_STREAMS * MUAVTA_RNG_WORDS * 4 : 0;
-  if (!e || !dst || bytes != need) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  HIPCHK(e, hipMemcpyAsync(dst, e->tapes, bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-int muavta_set_rng(MuavtaEnv* e, const void* src, size_t bytes) {
-  size_t need = e ? (size_t)e->n_envs * MUAVTA_RNG_STREAMS * MUAVTA_RNG_WORDS * 4 : 0;
-  if (!e || !src || bytes != need) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  HIPCHK(e, hipMemcpyAsync(e->tapes, src, bytes, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-
-int muavta_device_ptrs(MuavtaEnv* e, void** state, void** obs_tasks, void** obs_legal, void** obs_agents, void** metrics, void** stream) {
-  if (!e) return MUAVTA_E_ARG;
-  if (state) *state = e->blobs;
-  if (obs_tasks) *obs_tasks = e->O.tasks;
-  if (obs_legal) *obs_legal = e->O.legal;
-  if (obs_agents) *obs_agents = e->O.agents;
-  if (metrics) *metrics = e->d_metrics;
-  if (stream) *stream = (void*)e->stream;
-  return MUAVTA_OK;
-}
-
-int muavta_rollout_metrics(MuavtaEnv* e, double* out) {  // metrics written by the last muavta_rollout (no extra kernel)
-  if (!e || !out) return MUAVTA_E_ARG;
-  DeviceScope scope_(e->device);
-  MAIN_OP(e);
-  HIPCHK(e, hipMemcpyAsync(out, e->d_metrics, (size_t)e->n_envs * MUAVTA_N_METRICS * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return MUAVTA_OK;
-}
-
-// the lane that holds the rollout launched just before the latest one, if that launch ran on the OTHER lane (else nullptr: overwritten)
-static MuavtaEnv* prev_batch_lane(MuavtaEnv* e) {
-  if (!e->hl.twin || e->hl.n_launches < 2) return nullptr;
-  const int R = MuavtaEnv::HandleLevel::RING;
-  const int last = e->hl.ring_lane[(e->hl.n_launches - 1) % R], prev = e->hl.ring_lane[(e->hl.n_launches - 2) % R];
-  if (last == prev) return nullptr;
-  MuavtaEnv* t = lane_by_id(e, prev);
-  return (t && t != e && t->n_rollouts == e->hl.ring_no[(e->hl.n_launches - 2) % R] + 1) ? t : nullptr;  // (and nothing else was launched on that lane since)
-}
-int muavta_rollout_metrics_back(MuavtaEnv* e, int32_t back, double* out) {  // back 0: the last seeded batch (= muavta_rollout_metrics); 1: the one before it, on the other lane
-  if (!e || !out || back < 0 || back > 1) return MUAVTA_E_ARG;
-  if (back == 0) return muavta_rollout_metrics(e, out);
-  MuavtaEnv* t = prev_batch_lane(e);
-  if (!t) { e->err = "muavta_rollout_metrics_back: the batch before the latest one is gone — it ran on the same lane (the latest rollout found it finished, or there is one lane only); muavta_set_lanes(h, 2) makes seeded rollouts always alternate"; return MUAVTA_E_STATE; }
-  int rc = muavta_rollout_metrics(t, out);
-  if (rc) e->err = t->err;
-  return rc;
-}
-int muavta_error_flags_back(MuavtaEnv* e, int32_t back, int32_t* out) {  // MUAVTA_F_ERROR of the batch `back` launches ago (0 or 1)
-  if (!e || !out || back < 0 || back > 1) return MUAVTA_E_ARG;
-  MuavtaEnv* L = back == 0 ? e : prev_batch_lane(e);
-  if (!L) { e->err = "muavta_error_flags_back: the batch before the latest one is gone (it ran on the same lane)"; return MUAVTA_E_STATE; }
-  int rc = muavta_get(L, MUAVTA_F_ERROR, out, (size_t)L->n_envs * sizeof(int32_t));
-  if (rc && L != e) e->err = L->err;
-  return rc;
-}
-int muavta_set_slot_cap(MuavtaEnv* e, int32_t cap) {  // test hook: an env may use at most `cap` of its tile's task slots (0: all of them)
-  if (!e || cap < 0 || cap > e->T) { if (e) e->err = "muavta_set_slot_cap: 0 .. the tile's slot count"; return MUAVTA_E_ARG; }
-  DeviceScope scope_(e->device);
-  if (e->hl.twin) { int rc = muavta_set_slot_cap(e->hl.twin, cap); if (rc) { e->err = e->hl.twin->err; return rc; } }
-  MAIN_OP(e);
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  e->P.slot_cap = (cap > 0 && cap < e->T) ? cap : 0;
-  HIPCHK(e, hipMemcpy((char*)e->d_ctx + offsetof(DevCtx, P) + offsetof(DevParams, slot_cap), &e->P.slot_cap, sizeof(int32_t), hipMemcpyHostToDevice));
-  return MUAVTA_OK;
-}
-int muavta_set_lanes(MuavtaEnv* e, int32_t lanes) {
-  if (!e || lanes < 0 || lanes > 2) { if (e) e->err = "muavta_set_lanes: 0 (second lane on demand), 1 (one lane) or 2 (always alternate)"; return MUAVTA_E_ARG; }
-  DeviceScope scope_(e->device);
-  if (lanes == 2) { int rc = ensure_twin(e); if (rc) { e->err = "muavta_set_lanes: the second lane could not be created: " + g_create_error; return rc; } }
-  if (lanes == 1 && e->hl.twin) {  // back to one lane: the second lane's batch completes and its memory is released
-    muavta_destroy(e->hl.twin);
-    e->hl.twin = nullptr;
-  }
-  e->hl.lanes_mode = lanes;
-  return MUAVTA_OK;
-}
-int muavta_lanes(const MuavtaEnv* e, int32_t* mode, int32_t* allocated) {
-  if (!e) return MUAVTA_E_ARG;
-  if (mode) *mode = e->hl.lanes_mode;
-  if (allocated) *allocated = e->hl.twin ? 2 : 1;
-  return MUAVTA_OK;
-}
-
-int muavta_lsap(int32_t device, const double* cost, int32_t n, int32_t nr, int32_t nc, int64_t* row, int64_t* col) {
-  return muavta_lsap_impl(device, cost, n, nr, nc, row, col, MUAVTA_LSAP_AUTO);
-}
-int muavta_lsap_impl(int32_t device, const double* cost, int32_t n, int32_t nr, int32_t nc, int64_t* row, int64_t* col, int32_t impl) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "muavta_lsap: no HIP device"; return MUAVTA_E_NO_DEVICE; }
-  if (!cost || !row || !col || n < 1 || nr < 1 || nc < 1) { g_create_error = "muavta_lsap: bad arguments"; return MUAVTA_E_ARG; }
-  int mn = nr < nc ? nr : nc, mx = nr < nc ? nc : nr;
-  if (mn > Tile64::A || mx > Tile64::T) { g_create_error = "muavta_lsap: at most 64 x 128"; return MUAVTA_E_ARG; }
-  // scipy.optimize.linear_sum_assignment raises ValueError("matrix contains invalid numeric entries") for NaN / -inf
-  for (size_t i = 0, m = (size_t)n * nr * nc; i < m; i++)
-    if (std::isnan(cost[i]) || cost[i] == -INFINITY) { g_create_error = "muavta_lsap: matrix contains invalid numeric entries (NaN or -inf)"; return MUAVTA_E_ARG; }
-  const bool fits_reg = mn <= TileLsapReg::A && mx <= TileLsapReg::T;
-  if (impl < MUAVTA_LSAP_AUTO || impl > MUAVTA_LSAP_REGISTERS || (impl == MUAVTA_LSAP_REGISTERS && !fits_reg)) {
-    g_create_error = "muavta_lsap_impl: unknown solver, or problem beyond 32 x 64 for the register solver"; return MUAVTA_E_ARG;
-  }
-  const bool use_reg = impl == MUAVTA_LSAP_REGISTERS || (impl == MUAVTA_LSAP_AUTO && fits_reg);
-#define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_create_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipFree(dc); hipFree(dr); hipFree(dcl); hipFree(dst); return MUAVTA_E_HIP; } } while (0)
-  double* dc = nullptr; int64_t *dr = nullptr, *dcl = nullptr; int32_t* dst = nullptr;
-  DeviceScope scope_(device);
-  size_t cb = (size_t)n * nr * nc * sizeof(double), rb = (size_t)n * mn * sizeof(int64_t);
-  CK(hipMalloc(&dc, cb)); CK(hipMalloc(&dr, rb)); CK(hipMalloc(&dcl, rb)); CK(hipMalloc(&dst, (size_t)n * sizeof(int32_t)));
-  CK(hipMemcpy(dc, cost, cb, hipMemcpyHostToDevice));
-  if (use_reg) {
-    size_t lds = Lds<TileLsapReg>::bytes();
-    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lsap<TileLsapReg, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_lsap<TileLsapReg, true>), dim3(n), dim3(WG), lds, 0, dc, nr, nc, dr, dcl, dst);
-  } else {
-    size_t lds = Lds<TileLsapLds>::bytes();
-    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lsap<TileLsapLds, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_lsap<TileLsapLds, false>), dim3(n), dim3(WG), lds, 0, dc, nr, nc, dr, dcl, dst);
-  }
-  CK(hipGetLastError());
-  std::vector<int32_t> status((size_t)n);
-  CK(hipMemcpy(status.data(), dst, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  CK(hipMemcpy(row, dr, rb, hipMemcpyDeviceToHost));
-  CK(hipMemcpy(col, dcl, rb, hipMemcpyDeviceToHost));
-#undef CK
-  hipFree(dc); hipFree(dr); hipFree(dcl); hipFree(dst);
-  for (int i = 0; i < n; i++)
-    if (status[(size_t)i]) {  // scipy: ValueError("cost matrix is infeasible")
-      g_create_error = "muavta_lsap: cost matrix " + std::to_string(i) + " is infeasible";
-      return MUAVTA_E_ARG;
-    }
-  return MUAVTA_OK;
-}
-
-int muavta_domain_math(int32_t device, const double* x, const double* y, int32_t n, double* out_sqrt, double* out_div, double* out_div_neg) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "muavta_domain_math: no HIP device"; return MUAVTA_E_NO_DEVICE; }
-  if (!x || !y || !out_sqrt || !out_div || !out_div_neg || n < 1) return MUAVTA_E_ARG;
-  double* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-#define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_create_error = std::string(#expr) + ": " + hipGetErrorString(e_); for (double* q : d) hipFree(q); return MUAVTA_E_HIP; } } while (0)
-  DeviceScope scope_(device);
-  const size_t bytes = (size_t)n * sizeof(double);
-  for (double*& q : d) CK(hipMalloc(&q, bytes));
-  CK(hipMemcpy(d[0], x, bytes, hipMemcpyHostToDevice));
-  CK(hipMemcpy(d[1], y, bytes, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_domain_math, dim3((n + 255) / 256), dim3(256), 0, 0, d[0], d[1], n, d[2], d[3], d[4]);
-  CK(hipGetLastError());
-  CK(hipMemcpy(out_sqrt, d[2], bytes, hipMemcpyDeviceToHost));
-  CK(hipMemcpy(out_div, d[3], bytes, hipMemcpyDeviceToHost));
-  CK(hipMemcpy(out_div_neg, d[4], bytes, hipMemcpyDeviceToHost));
-#undef CK
-  for (double* q : d) hipFree(q);
-  return MUAVTA_OK;
-}
-
-int muavta_domain_log(int32_t device, const double* x, int32_t n, double* out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "muavta_domain_log: no HIP device"; return MUAVTA_E_NO_DEVICE; }
-  if (!x || !out || n < 1) return MUAVTA_E_ARG;
-  double* d[2] = {nullptr, nullptr};
-#define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_create_error = std::string(#expr) + ": " + hipGetErrorString(e_); for (double* q : d) hipFree(q); return MUAVTA_E_HIP; } } while (0)
-  DeviceScope scope_(device);
-  const size_t bytes = (size_t)n * sizeof(double);
-  for (double*& q : d) CK(hipMalloc(&q, bytes));
-  CK(hipMemcpy(d[0], x, bytes, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_libm_log, dim3((n + 255) / 256), dim3(256), 0, 0, d[0], n, d[1]);
-  CK(hipGetLastError());
-  CK(hipMemcpy(out, d[1], bytes, hipMemcpyDeviceToHost));
-#undef CK
-  for (double* q : d) hipFree(q);
-  return MUAVTA_OK;
-}
-
-int muavta_domain_atan2(int32_t device, const double* y, const double* x, int32_t n, double* out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "muavta_domain_atan2: no HIP device"; return MUAVTA_E_NO_DEVICE; }
-  if (!x || !y || !out || n < 1) return MUAVTA_E_ARG;
-  double* d[3] = {nullptr, nullptr, nullptr};
-#define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_create_error = std::string(#expr) + ": " + hipGetErrorString(e_); for (double* q : d) hipFree(q); return MUAVTA_E_HIP; } } while (0)
-  DeviceScope scope_(device);
-  const size_t bytes = (size_t)n * sizeof(double);
-  for (double*& q : d) CK(hipMalloc(&q, bytes));
-  CK(hipMemcpy(d[0], y, bytes, hipMemcpyHostToDevice));
-  CK(hipMemcpy(d[1], x, bytes, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_libm_atan2, dim3((n + 255) / 256), dim3(256), 0, 0, d[0], d[1], n, d[2]);
-  CK(hipGetLastError());
-  CK(hipMemcpy(out, d[2], bytes, hipMemcpyDeviceToHost));
-#undef CK
-  for (double* q : d) hipFree(q);
-  return MUAVTA_OK;
-}
-
-int muavta_avoid_obstacles(int32_t device, const double* agent_pos, const double* movement, int32_t n, const double* obstacles,
-                           int32_t n_obstacles, double* out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "muavta_avoid_obstacles: no HIP device"; return MUAVTA_E_NO_DEVICE; }
-  if (!agent_pos || !movement || !out || n < 1 || n_obstacles < 0 || (n_obstacles > 0 && !obstacles)) return MUAVTA_E_ARG;
-  double *dp = nullptr, *dm = nullptr, *dob = nullptr, *dout = nullptr;
-#define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_create_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipFree(dp); hipFree(dm); hipFree(dob); hipFree(dout); return MUAVTA_E_HIP; } } while (0)
-  DeviceScope scope_(device);
-  CK(hipMalloc(&dp, (size_t)n * 16)); CK(hipMalloc(&dm, (size_t)n * 16)); CK(hipMalloc(&dout, (size_t)n * 16));
-  CK(hipMalloc(&dob, (size_t)(n_obstacles > 0 ? n_obstacles : 1) * 24));
-  CK(hipMemcpy(dp, agent_pos, (size_t)n * 16, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dm, movement, (size_t)n * 16, hipMemcpyHostToDevice));
-  if (n_obstacles > 0) CK(hipMemcpy(dob, obstacles, (size_t)n_obstacles * 24, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_avoid, dim3((n + 255) / 256), dim3(256), 0, 0, dp, dm, n, dob, n_obstacles, dout);
-  CK(hipGetLastError());
-  CK(hipMemcpy(out, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
-#undef CK
-  hipFree(dp); hipFree(dm); hipFree(dob); hipFree(dout);
-  return MUAVTA_OK;
-}
-
-}  // extern "C"
+#include "abi/handle.inc"
+#include "abi/sim.inc"
+#include "abi/state.inc"
+#include "abi/comm.inc"
+#include "abi/probes.inc"

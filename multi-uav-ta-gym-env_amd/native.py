@@ -59,8 +59,8 @@ class MuavtaPairMlp(C.Structure):
 
 def sources():
     """every file the shipped library is compiled from (muavta_diag.h is not one of them: diagnostic builds only)"""
-    sim = sorted(os.path.join(CSRC, "sim", f) for f in os.listdir(os.path.join(CSRC, "sim")) if f.endswith(".inc"))
-    return [os.path.join(CSRC, f) for f in ("muavta_kernels.hip", "muavta_device.h", "muavta_state.h", "muavta_math.h", "muavta_atan2.h", "muavta_atan2_tab.inc", "muavta_rng.h")] + sim + [
+    inc = [os.path.join(CSRC, d, f) for d in ("sim", "abi") for f in sorted(os.listdir(os.path.join(CSRC, d))) if f.endswith(".inc")]
+    return [os.path.join(CSRC, f) for f in ("muavta_kernels.hip", "muavta_device.h", "muavta_state.h", "muavta_math.h", "muavta_atan2.h", "muavta_atan2_tab.inc", "muavta_rng.h")] + inc + [
         os.path.join(os.path.dirname(PKG_DIR), "include", "muavta.h")]
 
 

@@ -1990,6 +1990,48 @@ def test_rl_step_by_sub_batches_equals_the_whole_batch_launch():
     assert np.array_equal(a.get("AGENT_POS"), b.get("AGENT_POS"))
 
 
+def test_rl_run_by_sub_batches_equals_the_whole_batch_launch():
+    """MuavtaRlStep.part in muavta_rl_run_device: the run to the next gate launched per sub-batch on the parts' own streams leaves the same
+    tensors (next and park tokens included) and the same env state as one launch over the whole batch."""
+    import torch
+
+    case, n, mt, ma = "WPS_hard", 6, 32, 16
+    a, b = _env(case, n), _env(case, n)
+    seeds = np.arange(11, 11 + n, dtype=np.uint64)
+    a.reset(seeds); b.reset(seeds)
+    b.set_parts(3)
+    dev = torch.device("cuda", 0)
+    tdt = {np.float32: torch.float32, np.uint8: torch.uint8, np.int32: torch.int32}
+
+    def outs(env):
+        toks = lambda: {k: torch.zeros(sh, dtype=tdt[dt], device=dev) for k, (sh, dt) in env.token_shapes("pair", mt, ma).items()}
+        return {"next_tok": toks(), "park_tok": toks(), "selected": torch.zeros((n, ma, mt), dtype=torch.float32, device=dev),
+                "replanned": torch.zeros((n,), dtype=torch.int32, device=dev), "s_wps": torch.zeros((2, n), dtype=torch.float64, device=dev),
+                "done": torch.zeros((n,), dtype=torch.uint8, device=dev), "n_stepped": torch.zeros((n,), dtype=torch.int32, device=dev),
+                "park": torch.zeros((n,), dtype=torch.uint8, device=dev), "reward_sum": torch.zeros((n,), dtype=torch.float64, device=dev)}
+
+    oa, ob = outs(a), outs(b)
+    gen = torch.Generator(device=dev); gen.manual_seed(5)
+    stepped = 0
+    for t in range(10):
+        sc = ((torch.rand((n, ma, mt), generator=gen, device=dev) * 2 - 1) * 0.35).contiguous()
+        torch.cuda.synchronize()
+        a.rl_run("pair", mt, ma, edge_scores=sc, gate="trainer", replan_interval=10, max_steps=4, **oa)
+        for p in range(3):
+            b.rl_run("pair", mt, ma, edge_scores=sc, gate="trainer", replan_interval=10, max_steps=4, part=p, **ob)
+        a.sync(); b.wait_part(-1)
+        for k in ("selected", "replanned", "s_wps", "done", "n_stepped", "park", "reward_sum"):
+            assert torch.equal(oa[k], ob[k]), f"t={t}: {k}"
+        for which in ("next_tok", "park_tok"):
+            for k in oa[which]:
+                assert torch.equal(oa[which][k], ob[which][k]), f"t={t}: {which} {k}"
+        stepped += int(oa["n_stepped"].sum())
+    assert stepped >= 10 * n, "the launches were expected to step every env"
+    b.set_parts(0)
+    assert np.array_equal(a.metrics(), b.metrics())
+    assert np.array_equal(a.get("AGENT_POS"), b.get("AGENT_POS"))
+
+
 # ---- run to the next replan gate: muavta_rl_run_device / muavta_step_run ----------------------------------------------------------------
 @pytest.mark.parametrize("max_steps", [0, 4], ids=["to-the-gate", "at-most-4-steps"])
 @pytest.mark.parametrize("path", RL_FILES, ids=[os.path.basename(p)[3:-4] for p in RL_FILES])
