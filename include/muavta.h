@@ -243,7 +243,8 @@ int muavta_step_staged(MuavtaEnv* env); /* step with the actions muavta_allocate
  *   MUAVTA_ALLOC_URGENCY_PAIR does with its engineered score (TaskAllocation/Hybrid/PairCostHybrid.py:154-197,266-278,308-328;
  *   experiments/wps_eval.py:244-254,490-492 with interval 15; train_pair_cost.py:73-93 with 20).  The plan is muavta_allocate_scored's
  *   with kind = MUAVTA_TOK_PAIR(_RAW), max_agents 16, max_tasks 32, MUAVTA_SC_EDGE_VALID_ONLY, MUAVTA_GATE_TRAINER; n_replans counts the
- *   HungarianAllocator's plans, as in MUAVTA_ALLOC_URGENCY_PAIR.  Needs muavta_set_pair_policy first (else MUAVTA_E_STATE); kernel
+ *   HungarianAllocator's plans, as in MUAVTA_ALLOC_URGENCY_PAIR.  Needs muavta_set_pair_policy first (else MUAVTA_E_STATE) — or
+ *   muavta_set_context_pair_policy: the mode runs the installed learned pair policy, MLP-Pair or MLP-ContextPair (below); kernel
  *   instantiations of its own; muavta_rollout_record returns MUAVTA_E_ARG.  Attention nets (AttPairNet), exploration noise and the
  *   value head are out of scope. */
 enum { MUAVTA_ALLOC_HUNGARIAN = 0, MUAVTA_ALLOC_URGENCY_PAIR = 1, MUAVTA_ALLOC_URGENCY_COALITION = 2, MUAVTA_ALLOC_HUNGARIAN_GATED = 3,
@@ -271,6 +272,37 @@ typedef struct MuavtaPairMlp {
 int muavta_set_pair_policy(MuavtaEnv* env, const MuavtaPairMlp* spec);
 int muavta_pair_scores(MuavtaEnv* env, float* scores, float* logits);
 int muavta_pair_scores_device(MuavtaEnv* env, float* scores, float* logits);
+
+/* MLP-ContextPair: ContextPairHybrid(use_attention=False) (TaskAllocation/Hybrid/ContextPairHybrid.py:154-210,213-240).  It inherits
+ * PairCostHybrid.plan — the tokens, edge_valid, the scored Hungarian and the gate are MUAVTA_ALLOC_MLP_PAIR's — and differs in the
+ * network: pair_mlp = Linear(K, 192) - ReLU - Linear(192, 192) - ReLU - Linear(192, 1) over
+ *     cat([agent_feats[i], task_feats[j], a_pool, t_pool, context]),   K = 2 * (12 + 13) + 8 = 58   (raw_features: 2 * (11 + 9) + 1 = 41)
+ * a_pool / t_pool: the masked means of the agent / task token rows, context: build_context_summary (muavta_context).  There is NO
+ * allocator number of its own: MUAVTA_ALLOC_MLP_PAIR runs the installed learned pair policy, and the handle holds ONE policy —
+ * muavta_set_pair_policy and muavta_set_context_pair_policy each replace whatever is installed, of either kind; the kind selects the
+ * kernel instantiation.  muavta_pair_scores(_device) serve both kinds with the same [N, 16, 32] outputs; muavta_rollout_record refuses
+ * the mode as before.  Semantics of the call as muavta_set_pair_policy: the weights (HOST pointers, state_dict layout, w0 [192, K] with
+ * the reference's column order) are copied, the call is ordered behind every launch queued on both state lanes and synchronises; if a
+ * lane cannot take the weights the previous policy is put back; a second lane created later gets its copy; NULL clears the policy
+ * (MUAVTA_E_STATE while MUAVTA_ALLOC_MLP_PAIR is selected).  hidden must be 192 (else MUAVTA_E_ARG).  ctx_mlp / value_mlp feed the
+ * value head only and are not part of the spec.  Attention and GNN variants (Att-ContextPair, GNN-ContextPair) are out of scope.
+ * ARITHMETIC (the device's definition, permanent: the tests compare logits bit for bit):
+ *   pools    for each feature column d: s = 0.0f; s = s + x[row][d] in float32 over the rows whose mask is 0 (non-pad), ascending row;
+ *            pool[d] = s / (float)max(count, 1), a correctly rounded IEEE float32 division.  a_pool over the 16 agent rows, t_pool over
+ *            the 32 task rows.
+ *   context  exactly what muavta_context(kind, 32, .) returns for the state.
+ *   layer 1  each of the 192 outputs is ONE float32 fmaf chain from the bias over a_pool, t_pool, context, the agent row, the task row
+ *            in this order, ascending within each: the env-uniform inputs come first, so the chain's value after them may be computed
+ *            once per env or once per pair with the same bits.  (Packing permutes the state_dict's columns accordingly.)
+ *   then     ReLU, layer 2 (k-ascending from the bias), layer 3 (n-ascending from the bias), score = tanhf(logit) * score_clamp on the
+ *            pairs whose edge_valid is 1, exactly as for MuavtaPairMlp.  Masked pairs are not evaluated; no value crosses lanes inside a
+ *            pair's chains: equal token rows in one env give bit-equal scores. */
+typedef struct MuavtaContextPairMlp {
+  int32_t raw_features, hidden;
+  float score_clamp;
+  const float *w0, *b0, *w1, *b1, *w2, *b2;
+} MuavtaContextPairMlp;
+int muavta_set_context_pair_policy(MuavtaEnv* env, const MuavtaContextPairMlp* spec);
 
 /* Token builders of the learned/engineered hybrids, batched over all envs straight from the device state
  * (SURVEY §8f rank 2).  kind:

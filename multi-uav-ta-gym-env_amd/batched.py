@@ -122,12 +122,18 @@ class BatchedMultiUAVEnv:
         two baseline modes rollout_record raises MuavtaError.
         'mlp_pair' (MLP-Pair: PairCostHybrid(use_attention=False).plan under _should_replan(env, events, replan_interval), the
         network's forward pass inside the kernel; wps_eval.py:244-254 with interval 15, train_pair_cost.py:73-93 with 20) needs
-        `set_pair_policy` first; rollout_record raises MuavtaError in it too."""
+        `set_pair_policy` first; rollout_record raises MuavtaError in it too.  The mode runs whatever learned pair policy is
+        installed, MLP-Pair or MLP-ContextPair (ContextPairHybrid(use_attention=False)); 'mlp_context_pair' is the same mode and
+        raises unless the installed policy is an MLP-ContextPair — a check on this object's record of its last `set_pair_policy`, not on the
+        handle: a policy installed or cleared through the C entry points directly is not seen by it."""
         mode = self.ALLOCATORS[name]
+        if name == "mlp_context_pair" and (getattr(self, "_pair_policy", None) or {}).get("kind") != "context":
+            raise MuavtaError("set_allocator('mlp_context_pair'): no MLP-ContextPair policy is installed (set_pair_policy with a ContextPairHybrid checkpoint first)")
         self._ck(self.L.muavta_set_allocator(self.h, mode))
         self._alloc_mode = mode
 
-    ALLOCATORS = {"hungarian": 0, "urgency_pair": 1, "urgency_coalition": 2, "hungarian_gated": 3, "cap_greedy": 4, "pi": 5, "mlp_pair": 6}
+    ALLOCATORS = {"hungarian": 0, "urgency_pair": 1, "urgency_coalition": 2, "hungarian_gated": 3, "cap_greedy": 4, "pi": 5, "mlp_pair": 6,
+                  "mlp_context_pair": 6}
     PAIR_MLP_KEYS = tuple(f"pair_mlp.{i}.{k}" for i in (0, 2, 4) for k in ("weight", "bias"))
 
     @classmethod
@@ -136,9 +142,17 @@ class BatchedMultiUAVEnv:
         'raw_features': bool, 'score_clamp': float, 'hidden': int}.  `src`: a path to a PairCostHybrid.save checkpoint (torch is
         imported only then), a state_dict-like mapping with pair_mlp.{0,2,4}.{weight,bias} (torch tensors or arrays; an optional
         'raw_features' / 'score_clamp' entry is honoured; a mapping with a 'state_dict' entry is a loaded checkpoint), or a PairCostHybrid.
-        Attention checkpoints (use_attention=True / AttPairNet) are refused.  Needs no device."""
+        Attention checkpoints (use_attention=True / AttPairNet) are refused.  Needs no device.
+        An MLP-ContextPair — a ContextPairHybrid.save checkpoint (kind == 'MLPContextPair'), a ContextPairHybrid(use_attention=False), or
+        a mapping whose pair_mlp.0.weight is [192, 58] (raw_features: [192, 41]) — is returned with 'kind': 'context' and 'hidden': 192
+        (an MLP-Pair with 'kind': 'pair'); its ctx_mlp.* / value_mlp.* entries feed the value head only and are ignored.
+        Att-ContextPair / GNN checkpoints are refused."""
         import os
         raw, clamp, sd = None, None, None
+        ck_kind = getattr(src, "kind", None) if hasattr(src, "net") else (src.get("kind") if hasattr(src, "keys") and "state_dict" in src.keys() else None)
+        if isinstance(ck_kind, str) and (ck_kind == "AttContextPair" or ck_kind.startswith("GNN")):
+            raise ValueError(f"set_pair_policy: a {ck_kind} policy is not supported; of the ContextPair hybrids only MLP-ContextPair runs on the device "
+                             "(Att-ContextPair and GNN-ContextPair do not)")
         if isinstance(src, (str, bytes, os.PathLike)):
             import torch
             try:  # PairCostHybrid.save writes a plain dict of tensors and scalars: nothing in it needs the unpickler to run code
@@ -146,6 +160,7 @@ class BatchedMultiUAVEnv:
             except Exception as exc:
                 raise ValueError(f"set_pair_policy: {src!r} is not a checkpoint of tensors and plain values (torch.load(weights_only=True): {exc}); "
                                  "load it yourself and pass the state_dict") from exc
+            return cls.parse_pair_policy(src, score_clamp)
         if hasattr(src, "net") and hasattr(src, "use_attention"):  # a PairCostHybrid
             if src.use_attention:
                 raise ValueError("set_pair_policy: use_attention=True (AttPairNet) is not supported; only the MLP variant runs on the device")
@@ -175,33 +190,44 @@ class BatchedMultiUAVEnv:
             return np.ascontiguousarray(v, dtype=np.float32)
         w0, b0, w1, b1, w2, b2 = (arr(k) for k in cls.PAIR_MLP_KEYS)
         hidden = b0.shape[0] if b0.ndim == 1 else -1
-        if w0.ndim != 2 or w0.shape[1] not in (20, 25) or (raw is not None and w0.shape[1] != (20 if raw else 25)):
+        context = w0.ndim == 2 and w0.shape[1] in (41, 58) and ck_kind in (None, "MLPContextPair")
+        if context:  # MLPContextPairNet.pair_mlp: agent, task, a_pool, t_pool, context columns
+            if raw is not None and w0.shape[1] != (41 if raw else 58):
+                raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {w0.shape}; an MLP-ContextPair has [192, 58] (raw_features: [192, 41])")
+            raw = w0.shape[1] == 41
+        elif w0.ndim != 2 or w0.shape[1] not in (20, 25) or (raw is not None and w0.shape[1] != (20 if raw else 25)) or ck_kind == "MLPContextPair":
             raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {w0.shape}; expected [hidden, 25] (raw_features: [hidden, 20])")
-        raw = w0.shape[1] == 20
+        else:
+            raw = w0.shape[1] == 20
         want = {"pair_mlp.0.weight": (hidden, w0.shape[1]), "pair_mlp.0.bias": (hidden,), "pair_mlp.2.weight": (hidden, hidden),
                 "pair_mlp.2.bias": (hidden,), "pair_mlp.4.weight": (1, hidden), "pair_mlp.4.bias": (1,)}
         for k, a in zip(cls.PAIR_MLP_KEYS, (w0, b0, w1, b1, w2, b2)):
             if a.shape != want[k]:
                 raise ValueError(f"set_pair_policy: {k} has shape {a.shape}; expected {want[k]}")
-        if hidden != 128:
+        if context and hidden != 192:
+            raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's MLP-ContextPair with hidden = 192 only")
+        if not context and hidden != 128:
             raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's hidden = 128 only")
         if score_clamp is not None:
             clamp = float(score_clamp)
         if clamp is None:
             clamp = 0.35  # SCORE_CLAMP (PairCostHybrid.py): the value every checkpoint of the reference is trained and saved with
-        return {"w0": w0, "b0": b0, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "raw_features": raw, "score_clamp": clamp, "hidden": hidden}
+        return {"w0": w0, "b0": b0, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "raw_features": raw, "score_clamp": clamp, "hidden": hidden,
+                "kind": "context" if context else "pair"}
 
     def set_pair_policy(self, src, score_clamp: Optional[float] = None):
-        """muavta_set_pair_policy: the network `set_allocator('mlp_pair')` and `pair_scores` run (see `parse_pair_policy` for `src`;
-        None clears it).  The weights are copied; a second call replaces them, also between rollouts."""
+        """muavta_set_pair_policy / muavta_set_context_pair_policy: the network `set_allocator('mlp_pair')` and `pair_scores` run (see
+        `parse_pair_policy` for `src`; None clears it).  The weights are copied; a second call replaces them — of either kind —
+        also between rollouts."""
         if src is None:
             self._ck(self.L.muavta_set_pair_policy(self.h, None))
             self._pair_policy = None
             return
         pol = self.parse_pair_policy(src, score_clamp)
-        spec = native.MuavtaPairMlp(int(pol["raw_features"]), int(pol["hidden"]), float(pol["score_clamp"]),
-                                    *(pol[k].ctypes.data for k in ("w0", "b0", "w1", "b1", "w2", "b2")))
-        self._ck(self.L.muavta_set_pair_policy(self.h, C.byref(spec)))
+        context = pol["kind"] == "context"
+        spec = (native.MuavtaContextPairMlp if context else native.MuavtaPairMlp)(
+            int(pol["raw_features"]), int(pol["hidden"]), float(pol["score_clamp"]), *(pol[k].ctypes.data for k in ("w0", "b0", "w1", "b1", "w2", "b2")))
+        self._ck((self.L.muavta_set_context_pair_policy if context else self.L.muavta_set_pair_policy)(self.h, C.byref(spec)))
         self._pair_policy = pol
 
     def pair_scores(self, out=None, want_logits: bool = False):

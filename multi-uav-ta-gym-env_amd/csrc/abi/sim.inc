@@ -35,8 +35,9 @@ struct AllocateKernel { AllocateFn fn; size_t lds; };
 template <class TL>
 using RolloutFn = void (*)(const DevCtx*, const uint64_t*, int, int, int, int, int, double*, const uint32_t*, const RecordPtrs<TL>*, int, int);
 template <class TL>
-RolloutFn<TL> rollout_kernel(bool recording, int alloc_mode) {  // (muavta_rollout_record refuses the modes past the Hungarian family)
+RolloutFn<TL> rollout_kernel(bool recording, int alloc_mode, int pol_kind) {  // (muavta_rollout_record refuses the modes past the Hungarian family)
   if (recording) return &k_rollout<TL, true>;
+  if (alloc_mode == MUAVTA_ALLOC_MLP_PAIR && pol_kind == POL_CONTEXT_PAIR) return &k_rollout<TL, false, false, true, true>;
   if (alloc_mode == MUAVTA_ALLOC_MLP_PAIR) return &k_rollout<TL, false, false, true>;
   if (alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) return &k_rollout<TL, false, true>;
   return &k_rollout<TL, false>;
@@ -92,7 +93,7 @@ static void launch_rollout(MuavtaEnv* e, const Target& t, const uint64_t* ds, in
     slot += MuavtaEnv::REC_SLOT;  // slot 1: the RecordPtrs of this launch
     hipLaunchKernelGGL(k_store_rec, dim3(1), dim3(64), 0, t.stream, blob, (uint32_t*)slot);
   }
-  const RolloutFn<TL> fn = rollout_kernel<TL>(rec != nullptr, e->alloc_mode);
+  const RolloutFn<TL> fn = rollout_kernel<TL>(rec != nullptr, e->alloc_mode, e->pol_kind);
   hipLaunchKernelGGL(fn, dim3(t.count), dim3(WG), extra_lds, t.stream, (const DevCtx*)e->d_ctx, ds, n_steps, interval, use_vis, e->alloc_mode, write_obs,
                      (double*)e->d_metrics, sb, (const RecordPtrs<TL>*)slot, epoch, t.first);
 }
@@ -209,7 +210,8 @@ int muavta_step_part(MuavtaEnv* e, int32_t part, const int32_t* act_agent, const
 
 static AllocateKernel allocate_kernel(MuavtaEnv* e) {
   AllocateKernel k{};
-  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
+  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR && e->pol_kind == POL_CONTEXT_PAIR) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
+  else if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
   else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, true>, Lds<TL>::bytes()}))
   else DISPATCH(e, (k = AllocateKernel{&k_allocate<TL>, Lds<TL>::bytes()}));
   return k;
@@ -441,7 +443,7 @@ int muavta_rollout_part(MuavtaEnv* e, int32_t part, int32_t n_steps, int32_t int
 int muavta_set_allocator(MuavtaEnv* e, int32_t mode) {
   if (!e || (mode < MUAVTA_ALLOC_HUNGARIAN || mode > MUAVTA_ALLOC_MLP_PAIR)) { if (e) e->err = "unknown allocator mode"; return MUAVTA_E_ARG; }
   if (mode == MUAVTA_ALLOC_MLP_PAIR && !e->hl.pol_set) {
-    e->err = "muavta_set_allocator: MUAVTA_ALLOC_MLP_PAIR needs a policy (muavta_set_pair_policy first)";
+    e->err = "muavta_set_allocator: MUAVTA_ALLOC_MLP_PAIR needs a policy (muavta_set_pair_policy first)";  // (or muavta_set_context_pair_policy)
     return MUAVTA_E_STATE;
   }
   e->alloc_mode = mode;

@@ -246,25 +246,83 @@ int check_errors(MuavtaEnv* e) {  // scan the per-env error words after a synchr
 
 }  // namespace
 
-// muavta_set_pair_policy on ONE lane: the lane's copy of the weights, its scratch and the `pol` words of its context, on the lane's
-// stream behind whatever it (and its part streams) still runs; synchronised, so the host vector may change afterwards.
+// muavta_set_pair_policy / muavta_set_context_pair_policy on ONE lane: the lane's copy of the weights, its scratch and the `pol` words of its
+// context, on the lane's stream behind whatever it (and its part streams) still runs; synchronised, so the host vector may change afterwards.
+// Both buffers are sized for the larger kind once, so a change of kind never frees memory that a queued launch may still read.
 static int push_policy(MuavtaEnv* l, const MuavtaEnv::HandleLevel& hl) {
   DeviceScope scope_(l->device);
   MAIN_OP(l);
   PairPolicyDev pd;
   memset(&pd, 0, sizeof(pd));
+  const size_t w_floats = PC_FLOATS > PW_FLOATS ? PC_FLOATS : PW_FLOATS;
   if (hl.pol_set) {
-    if (!l->d_pol_w) HIPCHK(l, l->d_pol_w.alloc((size_t)PW_FLOATS * sizeof(float)));
+    if (!l->d_pol_w) HIPCHK(l, l->d_pol_w.alloc(w_floats * sizeof(float)));
     if (!l->d_pol_scratch) {
-      HIPCHK(l, l->d_pol_scratch.alloc((size_t)l->n_envs * PS_FLOATS * sizeof(float)));
-      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch, 0, (size_t)l->n_envs * PS_FLOATS * sizeof(float), l->stream));
+      HIPCHK(l, l->d_pol_scratch.alloc((size_t)l->n_envs * PSC_FLOATS * sizeof(float)));
+      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch, 0, (size_t)l->n_envs * PSC_FLOATS * sizeof(float), l->stream));
     }
-    HIPCHK(l, hipMemcpyAsync(l->d_pol_w, hl.pol_w.data(), (size_t)PW_FLOATS * sizeof(float), hipMemcpyHostToDevice, l->stream));
-    pd.w = l->d_pol_w; pd.scratch = l->d_pol_scratch; pd.raw = hl.pol_raw; pd.clamp = hl.pol_clamp;
+    if (hl.pol_w.size() > w_floats) { l->err = "push_policy: packed weights larger than the lane's buffer"; return MUAVTA_E_ARG; }
+    HIPCHK(l, hipMemcpyAsync(l->d_pol_w, hl.pol_w.data(), hl.pol_w.size() * sizeof(float), hipMemcpyHostToDevice, l->stream));
+    pd.w = l->d_pol_w; pd.scratch = l->d_pol_scratch; pd.raw = hl.pol_raw; pd.clamp = hl.pol_clamp; pd.kind = hl.pol_kind;
   }
   HIPCHK(l, hipMemcpyAsync((char*)l->d_ctx.p + offsetof(DevCtx, pol), &pd, sizeof(pd), hipMemcpyHostToDevice, l->stream));
   HIPCHK(l, hipStreamSynchronize(l->stream));  // `pd` is a stack object
+  l->pol_kind = hl.pol_set ? hl.pol_kind : POL_PAIR;
   return MUAVTA_OK;
+}
+
+// The two setters' common part.  `who`: the entry point's name; `packed` (non-empty: install): the weights in the kind's device layout.
+// The handle holds ONE policy: either setter replaces whatever is installed, of either kind.
+static int install_policy(MuavtaEnv* e, const char* who, bool clear, int kind, int raw, float clamp, std::vector<float>& packed) {
+  // what the handle holds now: put back if the new policy does not reach BOTH lanes (the handle-level record must never say "set"
+  // while a lane's context holds no, or another, policy)
+  std::vector<float> old_w = e->hl.pol_w;
+  const int old_raw = e->hl.pol_raw, old_kind = e->hl.pol_kind;
+  const float old_clamp = e->hl.pol_clamp;
+  const bool old_set = e->hl.pol_set;
+  if (clear) {
+    if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) {
+      e->err = std::string(who) + ": the MLP-Pair allocator is selected; muavta_set_allocator to another mode before clearing its policy";
+      return MUAVTA_E_STATE;
+    }
+    e->hl.pol_set = false;
+    e->hl.pol_w.clear();
+  } else {
+    e->hl.pol_w.swap(packed);
+    e->hl.pol_kind = kind; e->hl.pol_raw = raw; e->hl.pol_clamp = clamp; e->hl.pol_set = true;
+  }
+  int rc = push_policy(e, e->hl);
+  if (rc == MUAVTA_OK && e->hl.twin) { rc = push_policy(e->hl.twin, e->hl); if (rc) e->err = e->hl.twin->err; }
+  if (rc == MUAVTA_OK) return MUAVTA_OK;
+  const std::string why = e->err;
+  e->hl.pol_w.swap(old_w); e->hl.pol_raw = old_raw; e->hl.pol_kind = old_kind; e->hl.pol_clamp = old_clamp; e->hl.pol_set = old_set;
+  int back = push_policy(e, e->hl);
+  if (back == MUAVTA_OK && e->hl.twin) back = push_policy(e->hl.twin, e->hl);
+  if (back != MUAVTA_OK) {  // not even the previous policy could be put back: no policy, and no mode that needs one
+    e->hl.pol_set = false;
+    e->hl.pol_w.clear();
+    if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) { e->alloc_mode = MUAVTA_ALLOC_HUNGARIAN; if (e->hl.twin) e->hl.twin->alloc_mode = MUAVTA_ALLOC_HUNGARIAN; }
+    e->err = std::string(who) + " failed (" + why + ") and the previous policy could not be restored: the handle has no policy now and runs the Hungarian allocator";
+    return rc;
+  }
+  e->err = std::string(who) + " failed, the previous policy is kept: " + why;
+  return rc;
+}
+
+// state_dict layout -> the device's: layer 1 k-major with device row k taken from column col0(k); layer 2 in groups of four interleaved outputs
+template <class LY, class Col0>
+static std::vector<float> pack_policy(size_t floats, int k0, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2, const float* b2, Col0 col0) {
+  const int H = LY::HID;
+  std::vector<float> w(floats, 0.f);
+  for (int n = 0; n < H; n++)
+    for (int k = 0; k < k0; k++) w[LY::W0 + (size_t)k * H + n] = w0[(size_t)n * k0 + col0(k)];  // k-major on the device
+  memcpy(&w[LY::B0], b0, H * sizeof(float));
+  for (int n = 0; n < H; n++)
+    for (int k = 0; k < H; k++) w[LY::W1 + ((size_t)(n / 4) * H + k) * 4 + n % 4] = w1[(size_t)n * H + k];  // four outputs interleaved
+  memcpy(&w[LY::B1], b1, H * sizeof(float));
+  memcpy(&w[LY::W2], w2, H * sizeof(float));
+  w[LY::B2] = b2[0];
+  return w;
 }
 
 extern "C" {
@@ -272,54 +330,33 @@ extern "C" {
 // ---- the learned MLP-Pair hybrid (sim/policy.inc) ---------------------------------------------------------------------------------
 int muavta_set_pair_policy(MuavtaEnv* e, const MuavtaPairMlp* spec) {
   if (!e) return MUAVTA_E_ARG;
-  // what the handle holds now: put back if the new policy does not reach BOTH lanes (the handle-level record must never say "set"
-  // while a lane's context holds no, or another, policy)
-  std::vector<float> old_w = e->hl.pol_w;
-  const int old_raw = e->hl.pol_raw;
-  const float old_clamp = e->hl.pol_clamp;
-  const bool old_set = e->hl.pol_set;
-  if (!spec) {  // clear
-    if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) {
-      e->err = "muavta_set_pair_policy: the MLP-Pair allocator is selected; muavta_set_allocator to another mode before clearing its policy";
-      return MUAVTA_E_STATE;
-    }
-    e->hl.pol_set = false;
-    e->hl.pol_w.clear();
-  } else {
+  std::vector<float> w;
+  if (spec) {
     if (spec->hidden != PW_HID || (spec->raw_features != 0 && spec->raw_features != 1) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 || !spec->w2 ||
         !spec->b2 || !(spec->score_clamp == spec->score_clamp)) {
       e->err = "muavta_set_pair_policy: bad spec (hidden must be 128, raw_features 0 or 1, six non-null arrays, score_clamp a number)";
       return MUAVTA_E_ARG;
     }
-    const int k0 = spec->raw_features ? 20 : 25;
-    std::vector<float> w((size_t)PW_FLOATS, 0.f);
-    for (int n = 0; n < PW_HID; n++)
-      for (int k = 0; k < k0; k++) w[PW_W0 + (size_t)k * PW_HID + n] = spec->w0[(size_t)n * k0 + k];  // k-major on the device
-    memcpy(&w[PW_B0], spec->b0, PW_HID * sizeof(float));
-    for (int n = 0; n < PW_HID; n++)
-      for (int k = 0; k < PW_HID; k++) w[PW_W1 + ((size_t)(n / 4) * PW_HID + k) * 4 + n % 4] = spec->w1[(size_t)n * PW_HID + k];  // four outputs interleaved
-    memcpy(&w[PW_B1], spec->b1, PW_HID * sizeof(float));
-    memcpy(&w[PW_W2], spec->w2, PW_HID * sizeof(float));
-    w[PW_B2] = spec->b2[0];
-    e->hl.pol_w.swap(w);
-    e->hl.pol_raw = spec->raw_features; e->hl.pol_clamp = spec->score_clamp; e->hl.pol_set = true;
+    w = pack_policy<PairLayout>(PW_FLOATS, spec->raw_features ? 20 : 25, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2, [](int k) { return k; });
   }
-  int rc = push_policy(e, e->hl);
-  if (rc == MUAVTA_OK && e->hl.twin) { rc = push_policy(e->hl.twin, e->hl); if (rc) e->err = e->hl.twin->err; }
-  if (rc == MUAVTA_OK) return MUAVTA_OK;
-  const std::string why = e->err;
-  e->hl.pol_w.swap(old_w); e->hl.pol_raw = old_raw; e->hl.pol_clamp = old_clamp; e->hl.pol_set = old_set;
-  int back = push_policy(e, e->hl);
-  if (back == MUAVTA_OK && e->hl.twin) back = push_policy(e->hl.twin, e->hl);
-  if (back != MUAVTA_OK) {  // not even the previous policy could be put back: no policy, and no mode that needs one
-    e->hl.pol_set = false;
-    e->hl.pol_w.clear();
-    if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) { e->alloc_mode = MUAVTA_ALLOC_HUNGARIAN; if (e->hl.twin) e->hl.twin->alloc_mode = MUAVTA_ALLOC_HUNGARIAN; }
-    e->err = "muavta_set_pair_policy failed (" + why + ") and the previous policy could not be restored: the handle has no policy now and runs the Hungarian allocator";
-    return rc;
+  return install_policy(e, "muavta_set_pair_policy", !spec, POL_PAIR, spec ? spec->raw_features : 0, spec ? spec->score_clamp : 0.f, w);
+}
+// MLP-ContextPair: the same, with MLPContextPairNet.pair_mlp.  The state_dict's columns are the reference's cat — agent, task, a_pool,
+// t_pool, context; the device's chain takes the env-uniform ones first (a_pool, t_pool, context, agent, task).
+int muavta_set_context_pair_policy(MuavtaEnv* e, const MuavtaContextPairMlp* spec) {
+  if (!e) return MUAVTA_E_ARG;
+  std::vector<float> w;
+  if (spec) {
+    if (spec->hidden != PC_HID || (spec->raw_features != 0 && spec->raw_features != 1) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 || !spec->w2 ||
+        !spec->b2 || !(spec->score_clamp == spec->score_clamp)) {
+      e->err = "muavta_set_context_pair_policy: bad spec (hidden must be 192, raw_features 0 or 1, six non-null arrays, score_clamp a number)";
+      return MUAVTA_E_ARG;
+    }
+    const int pairw = spec->raw_features ? 20 : 25, np = pairw + (spec->raw_features ? 1 : 8);  // agent + task columns; a_pool + t_pool + context columns
+    w = pack_policy<ContextPairLayout>(PC_FLOATS, pairw + np, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2,
+                                       [=](int k) { return k < np ? k + pairw : k - np; });
   }
-  e->err = "muavta_set_pair_policy failed, the previous policy is kept: " + why;
-  return rc;
+  return install_policy(e, "muavta_set_context_pair_policy", !spec, POL_CONTEXT_PAIR, spec ? spec->raw_features : 0, spec ? spec->score_clamp : 0.f, w);
 }
 int muavta_pair_scores_device(MuavtaEnv* e, float* scores, float* logits) {
   if (!e) return MUAVTA_E_ARG;
@@ -328,7 +365,8 @@ int muavta_pair_scores_device(MuavtaEnv* e, float* scores, float* logits) {
   if (!scores && !logits) return MUAVTA_OK;
   DeviceScope scope_(e->device);
   MAIN_OP(e);
-  DISPATCH(e, hipLaunchKernelGGL(k_pair_scores<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits));
+  if (e->pol_kind == POL_CONTEXT_PAIR) DISPATCH(e, hipLaunchKernelGGL((k_pair_scores<TL, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits))
+  else DISPATCH(e, hipLaunchKernelGGL(k_pair_scores<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits));
   HIPCHK(e, hipGetLastError());
   return MUAVTA_OK;
 }

@@ -142,7 +142,9 @@ struct PairPolicyDev {
   float* scratch;    // [N][PS_FLOATS]
   int32_t raw;       // checkpoint's raw_features: tokens of kind MUAVTA_TOK_PAIR_RAW (agent 11 + task 9) instead of MUAVTA_TOK_PAIR (12 + 13)
   float clamp;       // score_clamp
+  int32_t kind;      // POL_PAIR / POL_CONTEXT_PAIR: which network `w` holds (and which kernel instantiations run it).  Appended: nothing in front of it moves
 };
+enum { POL_PAIR = 0, POL_CONTEXT_PAIR = 1 };
 enum { PW_HID = 128, PW_W0_ROWS = 25,
        PW_W0 = 0, PW_B0 = PW_W0 + PW_HID * PW_W0_ROWS, PW_W1 = PW_B0 + PW_HID, PW_B1 = PW_W1 + PW_HID * PW_HID, PW_W2 = PW_B1 + PW_HID,
        PW_B2 = PW_W2 + PW_HID, PW_FLOATS = PW_B2 + 16 };
@@ -150,6 +152,17 @@ enum { PW_HID = 128, PW_W0_ROWS = 25,
 enum { PS_MA = 16, PS_MT = 32,
        PS_TF = 0, PS_AF = PS_TF + PS_MT * 13, PS_EV = PS_AF + PS_MA * 12, PS_SCORES = PS_EV + PS_MA * PS_MT, PS_TID = PS_SCORES + PS_MA * PS_MT,
        PS_AID = PS_TID + PS_MT, PS_TMASK = PS_AID + PS_MA, PS_AMASK = PS_TMASK + PS_MT / 4, PS_FLOATS = (PS_AMASK + PS_MA / 4 + 3) & ~3 };
+// muavta_set_context_pair_policy: MLPContextPairNet.pair_mlp, Linear(58|41, 192) - ReLU - Linear(192, 192) - ReLU - Linear(192, 1).  A packed-weight
+// layout of its own, in the same order (layer 1 k-major with its columns permuted to a_pool, t_pool, context, agent, task; layer 2 in
+// groups of four interleaved outputs), and a larger per-env scratch block: the MLP-Pair block, then the env-uniform head of layer 1's
+// input row — a_pool [12|11], t_pool [13|9], context [8|1], contiguous (PSC_PRE; sim/policy.inc: context_prefix) — and the 192 chains' values
+// after those inputs (PSC_HEAD: computed once per plan, every pair's chain continues from them).
+enum { PC_HID = 192, PC_W0_ROWS = 58,
+       PC_W0 = 0, PC_B0 = PC_W0 + PC_HID * PC_W0_ROWS, PC_W1 = PC_B0 + PC_HID, PC_B1 = PC_W1 + PC_HID * PC_HID, PC_W2 = PC_B1 + PC_HID,
+       PC_B2 = PC_W2 + PC_HID, PC_FLOATS = PC_B2 + 16 };
+enum { PSC_PRE = PS_FLOATS, PSC_HEAD = PSC_PRE + 36, PSC_FLOATS = PSC_HEAD + PC_HID };
+struct PairLayout { enum { CTX = 0, HID = PW_HID, W0_ROWS = PW_W0_ROWS, W0 = PW_W0, B0 = PW_B0, W1 = PW_W1, B1 = PW_B1, W2 = PW_W2, B2 = PW_B2 }; };
+struct ContextPairLayout { enum { CTX = 1, HID = PC_HID, W0_ROWS = PC_W0_ROWS, W0 = PC_W0, B0 = PC_B0, W1 = PC_W1, B1 = PC_B1, W2 = PC_W2, B2 = PC_B2 }; };
 
 template <class TL>
 struct Sim {

@@ -18,13 +18,16 @@
   typedef const __attribute__((address_space(4))) float pol_cf;  // constant address space: uniform indices become scalar loads
   typedef float pol_f2 __attribute__((ext_vector_type(2)));
   static DEV float pol_relu(float v) { return v > 0.f ? v : 0.f; }
+  static DEV const float* as_global_f(const float* p) { return (const float*)(const __attribute__((address_space(1))) float*)p; }
   // tf / af / ev: this env's token tensors ([32, Dt], [16, Da], [16, 32]) in global memory, complete and visible (cold_sync() by the
   // caller).  scores / logits: this env's [16, 32] outputs (either may be null).  fill: masked entries are written as 0 (the fused mode
   // leaves them alone: allocate<true> under MUAVTA_SC_EDGE_VALID_ONLY never reads them).  Scratch: X.cost .. X.spc (the list of valid cells).
-  template <bool RAW>
-  DEV void pair_forward_t(const PairPolicyDev& pol, const float* tf, const float* af, const float* ev, float* scores, float* logits, bool fill) {
-    constexpr int Da = RAW ? 11 : 12, Dt = RAW ? 9 : 13, K0 = Da + Dt, HID = PW_HID, CELLS = PS_MA * PS_MT;
-    static_assert(K0 <= PW_W0_ROWS && HID % 64 == 0, "layer 1's weights are stored k-major, PW_W0_ROWS rows of HID");
+  // LY: PairLayout (MLP-Pair, 128 wide) or ContextPairLayout (MLP-ContextPair, 192 wide; `pre`: the env-uniform head of layer 1's input row
+  // in the env's scratch block, context_prefix() below, with the 192 floats of PSC_HEAD behind it) — the packed-weight offsets and the width, everything else is the same code.
+  template <bool RAW, class LY>
+  DEV void pair_forward_t(const PairPolicyDev& pol, const float* tf, const float* af, const float* ev, float* scores, float* logits, bool fill, const float* pre) {
+    constexpr int Da = RAW ? 11 : 12, Dt = RAW ? 9 : 13, NP = LY::CTX ? Da + Dt + (RAW ? 1 : 8) : 0, K0 = NP + Da + Dt, HID = LY::HID, CELLS = PS_MA * PS_MT;
+    static_assert(K0 <= LY::W0_ROWS && HID % 64 == 0, "layer 1's weights are stored k-major, W0_ROWS rows of HID");
     // the list of valid cells: the cost tile and the LSAP's duals / spc behind it (one run of doubles, all idle between the token builder and the plan)
     static_assert(offsetof(Scratch<TL>, resid) - offsetof(Scratch<TL>, cost) >= CELLS * sizeof(uint16_t) && offsetof(Scratch<TL>, u) > offsetof(Scratch<TL>, cost) &&
                   offsetof(Scratch<TL>, resid) > offsetof(Scratch<TL>, spc), "the list of valid cells needs 1 KB in front of Scratch::resid");
@@ -43,6 +46,23 @@
         if (logits) logits[c] = 0.f;
       }
       nv += __popcll(m);
+    }
+    // CTX: the first NP inputs of layer 1 (a_pool, t_pool, context) are the same for every pair of the env, so the chains' values after them
+    // are computed ONCE per plan — output n on lane n % 64, the same fmaf steps in the same order, hence the same bits — and parked in the
+    // env's scratch block (PSC_HEAD); every pair's chain continues from there.  Written and read back with vector accesses: not through
+    // the scalar cache, which may still hold the line of the previous plan.
+    float* head = LY::CTX ? const_cast<float*>(pre) + (PSC_HEAD - PSC_PRE) : nullptr;
+    if constexpr (LY::CTX) {
+      if (nv > 0) {  // (uniform)
+        const float* wg = as_global_f(pol.w);
+        for (int n = lane; n < HID; n += WG) {
+          float acc = wg[LY::B0 + n];
+#pragma unroll 1
+          for (int k = 0; k < NP; k++) acc = __builtin_fmaf(wg[LY::W0 + k * HID + n], pre[k], acc);
+          head[n] = acc;
+        }
+      }
+      cold_sync();  // every lane's outputs are in memory before any lane reads another's
     }
     lds_sync();
     for (int b0 = 0; b0 < nv; b0 += WG) {  // (uniform)
@@ -64,11 +84,14 @@
 #pragma unroll
       for (int nc = 0; nc < HID / 2; nc += 32) {
 #pragma unroll
-        for (int t = 0; t < 32; t++) h1[nc + t] = pol_f2{w[PW_B0 + 2 * (nc + t)], w[PW_B0 + 2 * (nc + t) + 1]};
+        for (int t = 0; t < 32; t++) {
+          if constexpr (LY::CTX) h1[nc + t] = pol_f2{head[2 * (nc + t)], head[2 * (nc + t) + 1]};
+          else h1[nc + t] = pol_f2{w[LY::B0 + 2 * (nc + t)], w[LY::B0 + 2 * (nc + t) + 1]};
+        }
 #pragma unroll 1
-        for (int k = 0; k < K0; k++) {
-          const float xk = *(k < Da ? xa + k : xt + (k - Da));
-          pol_cf* r = w + PW_W0 + k * HID + 2 * nc;
+        for (int k = NP; k < K0; k++) {
+          const float xk = *(k < NP + Da ? xa + (k - NP) : xt + (k - NP - Da));
+          pol_cf* r = w + LY::W0 + k * HID + 2 * nc;
 #pragma unroll
           for (int t = 0; t < 32; t++) h1[nc + t] = __builtin_elementwise_fma(pol_f2{r[2 * t], r[2 * t + 1]}, pol_f2{xk, xk}, h1[nc + t]);
         }
@@ -77,19 +100,19 @@
         __builtin_amdgcn_sched_barrier(0);
       }
       // Layers 2 and 3 together: four of layer 2's chains side by side (outputs n .. n + 3, their weights interleaved in memory so
-      // that the four of one k are neighbours: PW_W1), eight k at a time, and layer 3's chain takes their outputs in ascending n
+      // that the four of one k are neighbours: LY::W1), eight k at a time, and layer 3's chain takes their outputs in ascending n
       // as they complete.  The weights of the NEXT eight k are requested right after the first products of a chunk have consumed
       // the current ones (scalar loads return out of order, so the wait in front of those products must find nothing else in
       // flight), and arrive while the chunk's other products issue.
-      float logit = w[PW_B2];
+      float logit = w[LY::B2];
 #pragma unroll 1
       for (int n = 0; n < HID; n += 4) {
-        pol_cf* r = w + PW_W1 + n * HID;  // [k][4]
+        pol_cf* r = w + LY::W1 + n * HID;  // [k][4]
         // (no instruction: the activations become new values in every iteration, so the (h, h) operand pairs below are formed where
         // they are used — as the packed FMA's operand select — instead of once in front of the loop in 128 more register pairs)
 #pragma unroll
         for (int q = 0; q < HID / 2; q++) asm volatile("" : "+v"(h1[q]));
-        pol_f2 a01 = pol_f2{w[PW_B1 + n], w[PW_B1 + n + 1]}, a23 = pol_f2{w[PW_B1 + n + 2], w[PW_B1 + n + 3]};
+        pol_f2 a01 = pol_f2{w[LY::B1 + n], w[LY::B1 + n + 1]}, a23 = pol_f2{w[LY::B1 + n + 2], w[LY::B1 + n + 3]};
         float cw[32];
 #pragma unroll
         for (int q = 0; q < 32; q++) cw[q] = r[q];
@@ -118,10 +141,10 @@
             for (int q = 0; q < 32; q++) cw[q] = dw[q];
           }
         }
-        logit = __builtin_fmaf(w[PW_W2 + n], pol_relu(a01.x), logit);
-        logit = __builtin_fmaf(w[PW_W2 + n + 1], pol_relu(a01.y), logit);
-        logit = __builtin_fmaf(w[PW_W2 + n + 2], pol_relu(a23.x), logit);
-        logit = __builtin_fmaf(w[PW_W2 + n + 3], pol_relu(a23.y), logit);
+        logit = __builtin_fmaf(w[LY::W2 + n], pol_relu(a01.x), logit);
+        logit = __builtin_fmaf(w[LY::W2 + n + 1], pol_relu(a01.y), logit);
+        logit = __builtin_fmaf(w[LY::W2 + n + 2], pol_relu(a23.x), logit);
+        logit = __builtin_fmaf(w[LY::W2 + n + 3], pol_relu(a23.y), logit);
       }
       if (act) {
         if (logits) logits[c] = logit;
@@ -131,8 +154,45 @@
     lds_sync();
   }
   DEV void pair_forward(const PairPolicyDev& pol, const float* tf, const float* af, const float* ev, float* scores, float* logits, bool fill) {
-    if (pol.raw) pair_forward_t<true>(pol, tf, af, ev, scores, logits, fill);  // (uniform)
-    else pair_forward_t<false>(pol, tf, af, ev, scores, logits, fill);
+    if (pol.raw) pair_forward_t<true, PairLayout>(pol, tf, af, ev, scores, logits, fill, nullptr);  // (uniform)
+    else pair_forward_t<false, PairLayout>(pol, tf, af, ev, scores, logits, fill, nullptr);
+  }
+  // ---- MLP-ContextPair: ContextPairHybrid(use_attention=False) (TaskAllocation/Hybrid/ContextPairHybrid.py:154-210) --------------------
+  //   pair = cat([agent_feats[i], task_feats[j], a_pool, t_pool, context]);  logits = pair_mlp(pair)   Linear(58|41, 192) - ReLU - Linear(192, 192) - ReLU - Linear(192, 1)
+  // plan(), the tokens, edge_valid, the scored Hungarian and the gate are PairCostHybrid's.  CONTRACT (DESIGN.md §7.1; tests/context_pair_mlp_py.py):
+  //   * pool[d]: s = 0.0f; s = s + x[row][d] in float32 over the rows whose mask is 0, ascending row; pool[d] = s / (float)max(count, 1), IEEE division
+  //     (a_pool over the 16 agent rows, t_pool over the 32 task rows); context = what Sim::context(raw, 32, .) writes;
+  //   * layer 1: one fmaf chain per output from the bias over a_pool, t_pool, context, the agent row, the task row (each ascending) — the
+  //     env-uniform inputs first, the state_dict's columns (agent, task, a_pool, t_pool, context) are permuted when the weights are packed;
+  //   * ReLU, layers 2 and 3, tanhf, the masked pairs: as above.
+  // context_prefix: the 25 + 8 (raw: 20 + 1) env-uniform inputs into the env's scratch block behind the MLP-Pair layout (PSC_PRE).  One
+  // column per lane; the forward pass reads them back with vector loads (every lane the same address) and runs the chains' env-uniform
+  // head once per plan (pair_forward_t).
+  template <bool RAW>
+  DEV void context_prefix_t(float* base) {
+    constexpr int Da = RAW ? 11 : 12, Dt = RAW ? 9 : 13;
+    float* pre = base + PSC_PRE;
+    if (lane < Da + Dt) {
+      const bool ag = lane < Da;
+      const int d = ag ? lane : lane - Da, rows = ag ? PS_MA : PS_MT, D = ag ? Da : Dt;
+      const float* x = base + (ag ? PS_AF : PS_TF);
+      const uint8_t* pad = reinterpret_cast<const uint8_t*>(base + (ag ? PS_AMASK : PS_TMASK));
+      float s = 0.0f;
+      int count = 0;
+      for (int r = 0; r < rows; r++)
+        if (pad[r] == 0) { s = s + x[r * D + d]; count++; }
+      pre[lane] = s / (float)(count > 1 ? count : 1);
+    }
+    context(RAW ? 1 : 0, PS_MT, pre + Da + Dt);
+    cold_sync();  // the columns are in memory before the forward pass reads them across lanes
+  }
+  DEV void context_prefix(const PairPolicyDev& pol, float* base) {
+    if (pol.raw) context_prefix_t<true>(base);  // (uniform)
+    else context_prefix_t<false>(base);
+  }
+  DEV void context_pair_forward(const PairPolicyDev& pol, const float* base, float* scores, float* logits, bool fill) {
+    if (pol.raw) pair_forward_t<true, ContextPairLayout>(pol, base + PS_TF, base + PS_AF, base + PS_EV, scores, logits, fill, base + PSC_PRE);  // (uniform)
+    else pair_forward_t<false, ContextPairLayout>(pol, base + PS_TF, base + PS_AF, base + PS_EV, scores, logits, fill, base + PSC_PRE);
   }
   // build_pair_tokens(env, 32, 16[, raw]) of the current state into this env's scratch block
   DEV void pair_tokens_scratch(const PairPolicyDev& pol, float* base) {
@@ -151,10 +211,15 @@
   //     if _should_replan(env, events, interval):  tok = build_tokens(env); scores = score_tokens(tok); result = plan(.., scores=scores)
   // — tokens and scores only where the gate fires (uniform), then the scored Hungarian with the gate, the token pads and the flags the
   // reference's plan uses.  scratch: this env's PS_FLOATS block; sc_list: T bytes of LDS behind the tile (allocate<true>'s task list).
+  // CX: the installed policy is an MLP-ContextPair (scratch: this env's PSC_FLOATS block).
+  template <bool CX = false>
   DEV void allocate_mlp(int interval, int use_visibility, const PairPolicyDev& pol, float* scratch, uint8_t* sc_list) {
     if (gate_fires(MUAVTA_GATE_TRAINER, interval)) {
       pair_tokens_scratch(pol, scratch);
-      pair_forward(pol, scratch + PS_TF, scratch + PS_AF, scratch + PS_EV, scratch + PS_SCORES, nullptr, false);
+      if constexpr (CX) {
+        context_prefix(pol, scratch);
+        context_pair_forward(pol, scratch, scratch + PS_SCORES, nullptr, false);
+      } else pair_forward(pol, scratch + PS_TF, scratch + PS_AF, scratch + PS_EV, scratch + PS_SCORES, nullptr, false);
       cold_sync();  // the scores are in memory before the cost evaluation reads them across lanes
     }
     ScoredDev sc;

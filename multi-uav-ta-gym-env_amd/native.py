@@ -35,7 +35,7 @@ EXPORTS = [
     "muavta_step_part", "muavta_observe_part", "muavta_wait_part", "muavta_domain_math", "muavta_domain_log", "muavta_domain_atan2", "muavta_step_lists",
     "muavta_allocate_scored", "muavta_allocate_scored_device", "muavta_rl_step_device", "muavta_launch_gaps_ms",
     "muavta_rl_run_device", "muavta_step_run", "muavta_set_lanes", "muavta_lanes", "muavta_rollout_metrics_back", "muavta_error_flags_back", "muavta_set_slot_cap", "muavta_context", "muavta_context_device",
-    "muavta_set_pair_policy", "muavta_pair_scores", "muavta_pair_scores_device",
+    "muavta_set_pair_policy", "muavta_pair_scores", "muavta_pair_scores_device", "muavta_set_context_pair_policy",
 ]
 
 
@@ -55,6 +55,11 @@ class MuavtaPairMlp(C.Structure):
     """include/muavta.h: MuavtaPairMlp (muavta_set_pair_policy)."""
     _fields_ = [("raw_features", C.c_int32), ("hidden", C.c_int32), ("score_clamp", C.c_float)] + [
         (n, C.c_void_p) for n in ("w0", "b0", "w1", "b1", "w2", "b2")]
+
+
+class MuavtaContextPairMlp(C.Structure):
+    """include/muavta.h: MuavtaContextPairMlp (muavta_set_context_pair_policy)."""
+    _fields_ = MuavtaPairMlp._fields_
 
 
 def sources():
@@ -188,6 +193,7 @@ def lib() -> C.CDLL:
     L.muavta_context.argtypes = [vp, i32, i32, vp]
     L.muavta_context_device.argtypes = [vp, i32, i32, vp]
     L.muavta_set_pair_policy.argtypes = [vp, C.POINTER(MuavtaPairMlp)]
+    L.muavta_set_context_pair_policy.argtypes = [vp, C.POINTER(MuavtaContextPairMlp)]
     L.muavta_pair_scores.argtypes = [vp, vp, vp]
     L.muavta_pair_scores_device.argtypes = [vp, vp, vp]
     L.muavta_lanes.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
