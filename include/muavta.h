@@ -495,7 +495,7 @@ int muavta_rollout(MuavtaEnv* env, const uint64_t* seeds, int32_t n_steps, int32
 /* State lanes: episode batches in flight inside ONE handle.  A fused rollout launch lasts as long as its slowest env; the wave slots its early
  * finishers free stay empty until it ends.  The reference's evaluation loop runs episode after episode (experiments/wps_eval.py:528-546: cases x
  * seeds), so the next batch's work exists before this one has finished: a handle may own a SECOND complete set of per-batch device state (env
- * records, RNG tapes, observation buffers, metrics, streams, seeding slots), and a seeded muavta_rollout / muavta_rollout_record that is issued
+ * records, RNG tapes, observation buffers, metrics, main stream, seeding slots), and a seeded muavta_rollout / muavta_rollout_record that is issued
  * while the handle's previous seeded rollout is still running goes to the other lane — its workgroups start in the free wave slots (+3 % / +17 % /
  * +37 % env-steps/s on BASELINE configs 2 / 4 / 5).  Results are those of the same calls on one lane, bit for bit (env instances are independent).
  *   lanes 0 (default)  the second lane is created the first time a seeded rollout finds the previous one still running (a caller that
@@ -507,7 +507,10 @@ int muavta_rollout(MuavtaEnv* env, const uint64_t* seeds, int32_t n_steps, int32
  * not flip — use mode 2 for a pipeline that relies on reach-back), so `rollout(seeds[i + 1]); read batch i` keeps two batches in flight.  Settings
  * (allocator, sub-batches, release log, slot cap) and every muavta_wait_stream made before the second lane exists carry over to it when it is
  * created, and later ones reach both lanes; a flipped muavta_rollout_record pre-fills obs_done on the lane that runs it.  muavta_sync waits for both lanes; muavta_device_ptrs returns the current
- * lane's buffers (they change with every flip: fetch them again after a seeded rollout, or pin the handle to one lane).  Device memory per
+ * lane's buffers (they change with every flip: fetch them again after a seeded rollout, or pin the handle to one lane).  Streams: the handle's
+ * three hot streams (first lane, seeding, second lane) are created by muavta_create in front of every other stream, so that they sit on different
+ * hardware queues at HIP's default of four; the second lane runs on the third, seeds on it as well while two lanes alternate (the handle's seeding
+ * stream serves the one-lane mode) and creates sub-batch streams only when muavta_set_parts asks for them.  Device memory per
  * handle: lanes x n_envs x (MuavtaDims.state_bytes + 19,968 B of RNG tapes + the observation tensors + 240 B of metrics) + 8 MB. */
 int muavta_set_lanes(MuavtaEnv* env, int32_t lanes);
 int muavta_lanes(const MuavtaEnv* env, int32_t* mode, int32_t* allocated);
@@ -628,7 +631,7 @@ int muavta_rollout_record(MuavtaEnv* env, const uint64_t* seeds, int32_t n_steps
 /* Sub-batches.  The reference's loop is "observe -> decide -> env.step" for ONE env (experiments/wps_eval.py:112-133,273); a batch
  * stepped by one launch per env step ends every launch on its slowest env (one that replans) while the host can do nothing.
  * muavta_set_parts splits the handle's env range into n_parts contiguous parts (0 or 1: off; at most 8), each with its own
- * stream (created on first use; MUAVTA_EAGER_PART_STREAMS=n in the environment makes muavta_create create n of them up front —
+ * stream (created on first use; MUAVTA_EAGER_PART_STREAMS=n in the environment makes muavta_create create n of the first lane's up front —
  * HIP binds a stream to one of its GPU_MAX_HW_QUEUES hardware queues, 4 by default, when it first gets work, and two part streams
  * that land on one queue execute in order: see INTEGRATION.md): the *_part calls below are the per-step entry points for ONE part — asynchronous on that part's stream, so the host can
  * decide for part A while the device steps part B, and the parts' launches overlap on the device.  Results are identical to the
