@@ -244,8 +244,8 @@ int muavta_step_staged(MuavtaEnv* env); /* step with the actions muavta_allocate
  *   experiments/wps_eval.py:244-254,490-492 with interval 15; train_pair_cost.py:73-93 with 20).  The plan is muavta_allocate_scored's
  *   with kind = MUAVTA_TOK_PAIR(_RAW), max_agents 16, max_tasks 32, MUAVTA_SC_EDGE_VALID_ONLY, MUAVTA_GATE_TRAINER; n_replans counts the
  *   HungarianAllocator's plans, as in MUAVTA_ALLOC_URGENCY_PAIR.  Needs muavta_set_pair_policy first (else MUAVTA_E_STATE) — or
- *   muavta_set_context_pair_policy: the mode runs the installed learned pair policy, MLP-Pair or MLP-ContextPair (below); kernel
- *   instantiations of its own; muavta_rollout_record returns MUAVTA_E_ARG.  Attention nets (AttPairNet), exploration noise and the
+ *   muavta_set_context_pair_policy: the mode runs the installed learned policy, MLP-Pair, MLP-ContextPair or MLP-Coalition (below;
+ *   the last one with the escort tokens, the escort gate and commit locks instead); kernel instantiations of its own; muavta_rollout_record returns MUAVTA_E_ARG.  Attention nets (AttPairNet), exploration noise and the
  *   value head are out of scope. */
 enum { MUAVTA_ALLOC_HUNGARIAN = 0, MUAVTA_ALLOC_URGENCY_PAIR = 1, MUAVTA_ALLOC_URGENCY_COALITION = 2, MUAVTA_ALLOC_HUNGARIAN_GATED = 3,
        MUAVTA_ALLOC_CAP_GREEDY = 4, MUAVTA_ALLOC_PI = 5, MUAVTA_ALLOC_MLP_PAIR = 6 };
@@ -263,10 +263,27 @@ int muavta_set_allocator(MuavtaEnv* env, int32_t mode);
  * weights only: equal token rows give bit-equal scores.  Pairs whose edge_valid is 0 are not evaluated.
  * muavta_pair_scores: scores / logits f32 [N, 16, 32] of every env's CURRENT state (build_pair_tokens(env, 32, 16) + the forward pass,
  * the code the allocator mode runs at a replan); 0 where edge_valid is 0; either may be NULL.  Host buffers, synchronises.
- * muavta_pair_scores_device: device buffers, on the handle's stream, no synchronisation. */
+ * muavta_pair_scores_device: device buffers, on the handle's stream, no synchronisation.
+ * raw_features is the MUAVTA_TOK_* kind of the tokens the network consumes: 0 = MUAVTA_TOK_PAIR, 1 = MUAVTA_TOK_PAIR_RAW (an MLP-Pair, hidden
+ * 128), 2 = MUAVTA_TOK_ESCORT: an MLP-COALITION, AttentionEscort(use_attention=False) (TaskAllocation/Hybrid/AttentionEscort.py:326-367,
+ * 370-524; experiments/escort_eval.py:181-188): pair_mlp = Linear(38, 256) - ReLU - Linear(256, 256) - ReLU - Linear(256, 1) over
+ * cat([agent_feats[i], task_feats[j]]) of build_escort_tokens(env, 48, 16) (agent 16 + task 22 features); hidden must be 256, w0 is
+ * [256, 38].  Any other combination of raw_features and hidden: MUAVTA_E_ARG.  With it installed MUAVTA_ALLOC_MLP_PAIR does what
+ * run_escort_episode's MLP-Coalition branch does at a step: under escort_eval._should_replan(env, events, replan_interval)
+ * (MUAVTA_GATE_ESCORT) tokens, scores = sigmoid(clip(logits, -20, 20)) * edge_valid * non-pad, then _plan_from_scores =
+ * muavta_allocate_scored's plan with kind MUAVTA_TOK_ESCORT, max_tasks 48, max_agents 16 and MUAVTA_SC_COMMIT only (every non-pad
+ * pair carries its score, 0 where edge_valid is 0; committed agents are reserved; apply_agent_commits); n_replans is
+ * hung_force.n_replans.  No allocator number and no entry point of its own: the handle holds ONE learned policy, its kind selects
+ * the kernel instantiation.  value_mlp, exploration noise, commit_threshold, training and Att-Coalition are out of scope.
+ * ARITHMETIC of this kind (permanent: logits are compared bit for bit): layer 1 — each of the 256 outputs is one k-ascending float32
+ * fmaf chain from the bias over the agent row's 16 features, then the task row's 22; ReLU, layer 2 (k-ascending from the bias) and
+ * layer 3 (n-ascending from the bias) as above; score = 1.0f / (1.0f + expf(-fminf(fmaxf(logit, -20.0f), 20.0f))) in float32 with a
+ * correctly rounded division; score_clamp is IGNORED.  Pairs that are pad or whose edge_valid is 0 are not evaluated and report 0;
+ * equal token rows in one env give bit-equal scores; no value crosses lanes inside a pair's chains.
+ * Shapes of muavta_pair_scores(_device) by installed kind: MLP-Pair and MLP-ContextPair [N, 16, 32]; MLP-Coalition [N, 16, 48]. */
 typedef struct MuavtaPairMlp {
-  int32_t raw_features, hidden;
-  float score_clamp;
+  int32_t raw_features, hidden;  /* raw_features: the MUAVTA_TOK_* kind (0, 1: MLP-Pair, hidden 128; 2: MLP-Coalition, hidden 256) */
+  float score_clamp;             /* (ignored by an MLP-Coalition) */
   const float *w0, *b0, *w1, *b1, *w2, *b2;
 } MuavtaPairMlp;
 int muavta_set_pair_policy(MuavtaEnv* env, const MuavtaPairMlp* spec);
@@ -280,7 +297,7 @@ int muavta_pair_scores_device(MuavtaEnv* env, float* scores, float* logits);
  * a_pool / t_pool: the masked means of the agent / task token rows, context: build_context_summary (muavta_context).  There is NO
  * allocator number of its own: MUAVTA_ALLOC_MLP_PAIR runs the installed learned pair policy, and the handle holds ONE policy —
  * muavta_set_pair_policy and muavta_set_context_pair_policy each replace whatever is installed, of either kind; the kind selects the
- * kernel instantiation.  muavta_pair_scores(_device) serve both kinds with the same [N, 16, 32] outputs; muavta_rollout_record refuses
+ * kernel instantiation.  muavta_pair_scores(_device) serve both kinds with the same [N, 16, 32] outputs (an MLP-Coalition: [N, 16, 48]); muavta_rollout_record refuses
  * the mode as before.  Semantics of the call as muavta_set_pair_policy: the weights (HOST pointers, state_dict layout, w0 [192, K] with
  * the reference's column order) are copied, the call is ordered behind every launch queued on both state lanes and synchronises; if a
  * lane cannot take the weights the previous policy is put back; a second lane created later gets its copy; NULL clears the policy

@@ -125,15 +125,20 @@ class BatchedMultiUAVEnv:
         `set_pair_policy` first; rollout_record raises MuavtaError in it too.  The mode runs whatever learned pair policy is
         installed, MLP-Pair or MLP-ContextPair (ContextPairHybrid(use_attention=False)); 'mlp_context_pair' is the same mode and
         raises unless the installed policy is an MLP-ContextPair — a check on this object's record of its last `set_pair_policy`, not on the
-        handle: a policy installed or cleared through the C entry points directly is not seen by it."""
+        handle: a policy installed or cleared through the C entry points directly is not seen by it.
+        'mlp_coalition' (MLP-Coalition: AttentionEscort(use_attention=False).plan under escort_eval._should_replan(env, events,
+        replan_interval) — escort tokens 16 x 48, sigmoid scores, commit locks; experiments/escort_eval.py:181-188 with interval 12) is
+        the same mode again and raises unless the recorded policy is an MLP-Coalition."""
         mode = self.ALLOCATORS[name]
+        if name == "mlp_coalition" and (getattr(self, "_pair_policy", None) or {}).get("kind") != "coalition":
+            raise MuavtaError("set_allocator('mlp_coalition'): no MLP-Coalition policy is installed (set_pair_policy with an AttentionEscort(use_attention=False) checkpoint first)")
         if name == "mlp_context_pair" and (getattr(self, "_pair_policy", None) or {}).get("kind") != "context":
             raise MuavtaError("set_allocator('mlp_context_pair'): no MLP-ContextPair policy is installed (set_pair_policy with a ContextPairHybrid checkpoint first)")
         self._ck(self.L.muavta_set_allocator(self.h, mode))
         self._alloc_mode = mode
 
     ALLOCATORS = {"hungarian": 0, "urgency_pair": 1, "urgency_coalition": 2, "hungarian_gated": 3, "cap_greedy": 4, "pi": 5, "mlp_pair": 6,
-                  "mlp_context_pair": 6}
+                  "mlp_context_pair": 6, "mlp_coalition": 6}
     PAIR_MLP_KEYS = tuple(f"pair_mlp.{i}.{k}" for i in (0, 2, 4) for k in ("weight", "bias"))
 
     @classmethod
@@ -146,9 +151,24 @@ class BatchedMultiUAVEnv:
         An MLP-ContextPair — a ContextPairHybrid.save checkpoint (kind == 'MLPContextPair'), a ContextPairHybrid(use_attention=False), or
         a mapping whose pair_mlp.0.weight is [192, 58] (raw_features: [192, 41]) — is returned with 'kind': 'context' and 'hidden': 192
         (an MLP-Pair with 'kind': 'pair'); its ctx_mlp.* / value_mlp.* entries feed the value head only and are ignored.
-        Att-ContextPair / GNN checkpoints are refused."""
+        Att-ContextPair / GNN checkpoints are refused.
+        An MLP-Coalition — an AttentionEscort.save checkpoint (use_attention False, version 2, max_tasks 48, max_agents 16; hidden 256 by
+        its weights), an AttentionEscort(use_attention=False), or a mapping whose pair_mlp.0.weight is [256, 38] — is returned with 'kind':
+        'coalition', 'hidden': 256 and 'raw_features': 2 (the MUAVTA_TOK_ESCORT kind its tokens have); value_mlp.* is ignored and
+        score_clamp plays no part.  Att-Coalition is refused."""
         import os
         raw, clamp, sd = None, None, None
+        coalition = False
+        if hasattr(src, "net") and hasattr(src, "use_attention") and hasattr(src, "commit_threshold") and not hasattr(src, "raw_features"):  # an AttentionEscort
+            src = {"state_dict": src.net.state_dict(), "use_attention": bool(src.use_attention), "max_tasks": int(src.max_tasks),
+                   "max_agents": int(src.max_agents), "version": 2}
+        if hasattr(src, "keys") and "state_dict" in src.keys() and "version" in src.keys() and "raw_features" not in src.keys():  # AttentionEscort.save
+            if src.get("use_attention", True):
+                raise ValueError("set_pair_policy: an Att-Coalition policy (AttentionEscort with use_attention=True) is not supported; only MLP-Coalition runs on the device")
+            for key, want in (("version", 2), ("max_tasks", 48), ("max_agents", 16)):
+                if int(src.get(key, -1)) != want:
+                    raise ValueError(f"set_pair_policy: the MLP-Coalition checkpoint has {key} = {src.get(key)}; the device runs {key} = {want} only")
+            coalition = True
         ck_kind = getattr(src, "kind", None) if hasattr(src, "net") else (src.get("kind") if hasattr(src, "keys") and "state_dict" in src.keys() else None)
         if isinstance(ck_kind, str) and (ck_kind == "AttContextPair" or ck_kind.startswith("GNN")):
             raise ValueError(f"set_pair_policy: a {ck_kind} policy is not supported; of the ContextPair hybrids only MLP-ContextPair runs on the device "
@@ -190,8 +210,16 @@ class BatchedMultiUAVEnv:
             return np.ascontiguousarray(v, dtype=np.float32)
         w0, b0, w1, b1, w2, b2 = (arr(k) for k in cls.PAIR_MLP_KEYS)
         hidden = b0.shape[0] if b0.ndim == 1 else -1
-        context = w0.ndim == 2 and w0.shape[1] in (41, 58) and ck_kind in (None, "MLPContextPair")
-        if context:  # MLPContextPairNet.pair_mlp: agent, task, a_pool, t_pool, context columns
+        coalition = coalition or (w0.ndim == 2 and w0.shape[1] == 38 and ck_kind is None)
+        if coalition:  # MLPCoalitionNet.pair_mlp: agent 16 + task 22 columns
+            if w0.ndim != 2 or w0.shape[1] != 38:
+                raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {w0.shape}; an MLP-Coalition has [256, 38]")
+            if hidden != 256:
+                raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's MLP-Coalition with hidden = 256 only")
+        context = not coalition and w0.ndim == 2 and w0.shape[1] in (41, 58) and ck_kind in (None, "MLPContextPair")
+        if coalition:
+            raw = 2
+        elif context:  # MLPContextPairNet.pair_mlp: agent, task, a_pool, t_pool, context columns
             if raw is not None and w0.shape[1] != (41 if raw else 58):
                 raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {w0.shape}; an MLP-ContextPair has [192, 58] (raw_features: [192, 41])")
             raw = w0.shape[1] == 41
@@ -204,16 +232,18 @@ class BatchedMultiUAVEnv:
         for k, a in zip(cls.PAIR_MLP_KEYS, (w0, b0, w1, b1, w2, b2)):
             if a.shape != want[k]:
                 raise ValueError(f"set_pair_policy: {k} has shape {a.shape}; expected {want[k]}")
-        if context and hidden != 192:
+        if coalition:
+            pass
+        elif context and hidden != 192:
             raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's MLP-ContextPair with hidden = 192 only")
-        if not context and hidden != 128:
+        elif not context and hidden != 128:
             raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's hidden = 128 only")
         if score_clamp is not None:
             clamp = float(score_clamp)
         if clamp is None:
             clamp = 0.35  # SCORE_CLAMP (PairCostHybrid.py): the value every checkpoint of the reference is trained and saved with
         return {"w0": w0, "b0": b0, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "raw_features": raw, "score_clamp": clamp, "hidden": hidden,
-                "kind": "context" if context else "pair"}
+                "kind": "coalition" if coalition else "context" if context else "pair"}
 
     def set_pair_policy(self, src, score_clamp: Optional[float] = None):
         """muavta_set_pair_policy / muavta_set_context_pair_policy: the network `set_allocator('mlp_pair')` and `pair_scores` run (see
@@ -231,10 +261,10 @@ class BatchedMultiUAVEnv:
         self._pair_policy = pol
 
     def pair_scores(self, out=None, want_logits: bool = False):
-        """muavta_pair_scores: the policy's scores (and logits) f32 [N, 16, 32] of every env's current state, 0 where edge_valid
-        is 0.  numpy by default (synchronises); `out` = {'scores': t[, 'logits': t]} of contiguous CUDA torch tensors goes through
+        """muavta_pair_scores: the policy's scores (and logits) f32 [N, 16, 32] ([N, 16, 48] while the recorded policy is an
+        MLP-Coalition) of every env's current state, 0 where edge_valid is 0.  numpy by default (synchronises); `out` = {'scores': t[, 'logits': t]} of contiguous CUDA torch tensors goes through
         the device entry on the handle's stream without a sync and is returned."""
-        shape = (self.n_envs, 16, 32)
+        shape = (self.n_envs, 16, 48 if (getattr(self, "_pair_policy", None) or {}).get("kind") == "coalition" else 32)
         if out is not None:
             if not out:
                 raise ValueError("pair_scores: out must hold a 'scores' and / or a 'logits' tensor")

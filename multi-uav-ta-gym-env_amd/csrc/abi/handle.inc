@@ -83,6 +83,7 @@ struct MuavtaEnv {
   DevBuf<void> d_comm;    // [64 f64 send | 64 x n_ranks f64 recv | 64 i64 send | 64 i64 recv]
   DevBuf<double> d_metrics;
   DevBuf<float> d_pol_w, d_pol_scratch;  // muavta_set_pair_policy: this lane's copy of the packed weights, its per-env token / score scratch
+  DevBuf<float> d_pol_scratch_e;         // ... and the larger one of the MLP-Coalition kind ([N][PE_FLOATS]), allocated when such a policy first reaches the lane
   int pol_kind = POL_PAIR;               // ... and which network they hold (push_policy): selects the kernel instantiation of MUAVTA_ALLOC_MLP_PAIR on this lane
   ObsPtrs O{};  // the observation buffers as the kernels see them: views of obs_mem
   DevBuf<void> obs_mem[7];
@@ -127,7 +128,7 @@ struct MuavtaEnv {
     unsigned long long ring_no[RING] = {};      // ... as that lane's launch number
     unsigned long long n_launches = 0;
     std::vector<hipEvent_t> pending_waits;  // muavta_wait_stream events recorded while there was no second lane: one created later waits on them
-    // muavta_set_pair_policy / muavta_set_context_pair_policy: the ONE installed policy — its packed weights (PW_* / PC_* layout by pol_kind) as the
+    // muavta_set_pair_policy / muavta_set_context_pair_policy: the ONE installed policy — its packed weights (PW_* / PC_* / PWE_* layout by pol_kind) as the
     // caller last set them; a second lane created later gets its copy from here
     std::vector<float> pol_w;
     int pol_kind = POL_PAIR;
@@ -157,10 +158,12 @@ int launch_attr(MuavtaEnv* e) {
                         reinterpret_cast<const void*>(&k_tokens<TL>), reinterpret_cast<const void*>(&k_call<TL>), reinterpret_cast<const void*>(&k_context<TL>),
                         reinterpret_cast<const void*>(&k_allocate<TL, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, true>),
                         reinterpret_cast<const void*>(&k_pair_scores<TL>), reinterpret_cast<const void*>(&k_rollout<TL, false, false, true>),
-                        reinterpret_cast<const void*>(&k_pair_scores<TL, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, false, true, true>)};
+                        reinterpret_cast<const void*>(&k_pair_scores<TL, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, false, true, true>),
+                        reinterpret_cast<const void*>(&k_pair_scores<TL, false, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, false, true, false, true>)};
     for (const void* k : ks) HIPCHK(e, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate<TL, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
     HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate<TL, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
+    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate<TL, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
     HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate_scored<TL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
   }
   return MUAVTA_OK;

@@ -37,6 +37,7 @@ using RolloutFn = void (*)(const DevCtx*, const uint64_t*, int, int, int, int, i
 template <class TL>
 RolloutFn<TL> rollout_kernel(bool recording, int alloc_mode, int pol_kind) {  // (muavta_rollout_record refuses the modes past the Hungarian family)
   if (recording) return &k_rollout<TL, true>;
+  if (alloc_mode == MUAVTA_ALLOC_MLP_PAIR && pol_kind == POL_COALITION) return &k_rollout<TL, false, false, true, false, true>;
   if (alloc_mode == MUAVTA_ALLOC_MLP_PAIR && pol_kind == POL_CONTEXT_PAIR) return &k_rollout<TL, false, false, true, true>;
   if (alloc_mode == MUAVTA_ALLOC_MLP_PAIR) return &k_rollout<TL, false, false, true>;
   if (alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) return &k_rollout<TL, false, true>;
@@ -210,7 +211,8 @@ int muavta_step_part(MuavtaEnv* e, int32_t part, const int32_t* act_agent, const
 
 static AllocateKernel allocate_kernel(MuavtaEnv* e) {
   AllocateKernel k{};
-  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR && e->pol_kind == POL_CONTEXT_PAIR) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
+  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR && e->pol_kind == POL_COALITION) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true, false, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
+  else if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR && e->pol_kind == POL_CONTEXT_PAIR) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
   else if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
   else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, true>, Lds<TL>::bytes()}))
   else DISPATCH(e, (k = AllocateKernel{&k_allocate<TL>, Lds<TL>::bytes()}));

@@ -254,16 +254,21 @@ static int push_policy(MuavtaEnv* l, const MuavtaEnv::HandleLevel& hl) {
   MAIN_OP(l);
   PairPolicyDev pd;
   memset(&pd, 0, sizeof(pd));
-  const size_t w_floats = PC_FLOATS > PW_FLOATS ? PC_FLOATS : PW_FLOATS;
+  const size_t w_floats = PWE_FLOATS;
+  static_assert(PWE_FLOATS >= PC_FLOATS && PWE_FLOATS >= PW_FLOATS, "the lane's weight buffer holds the largest kind");
   if (hl.pol_set) {
     if (!l->d_pol_w) HIPCHK(l, l->d_pol_w.alloc(w_floats * sizeof(float)));
     if (!l->d_pol_scratch) {
       HIPCHK(l, l->d_pol_scratch.alloc((size_t)l->n_envs * PSC_FLOATS * sizeof(float)));
       HIPCHK(l, hipMemsetAsync(l->d_pol_scratch, 0, (size_t)l->n_envs * PSC_FLOATS * sizeof(float), l->stream));
     }
+    if (hl.pol_kind == POL_COALITION && !l->d_pol_scratch_e) {  // the escort-token block: only lanes that run this kind pay for it
+      HIPCHK(l, l->d_pol_scratch_e.alloc((size_t)l->n_envs * PE_FLOATS * sizeof(float)));
+      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch_e, 0, (size_t)l->n_envs * PE_FLOATS * sizeof(float), l->stream));
+    }
     if (hl.pol_w.size() > w_floats) { l->err = "push_policy: packed weights larger than the lane's buffer"; return MUAVTA_E_ARG; }
     HIPCHK(l, hipMemcpyAsync(l->d_pol_w, hl.pol_w.data(), hl.pol_w.size() * sizeof(float), hipMemcpyHostToDevice, l->stream));
-    pd.w = l->d_pol_w; pd.scratch = l->d_pol_scratch; pd.raw = hl.pol_raw; pd.clamp = hl.pol_clamp; pd.kind = hl.pol_kind;
+    pd.w = l->d_pol_w; pd.scratch = hl.pol_kind == POL_COALITION ? l->d_pol_scratch_e : l->d_pol_scratch; pd.raw = hl.pol_raw; pd.clamp = hl.pol_clamp; pd.kind = hl.pol_kind;
   }
   HIPCHK(l, hipMemcpyAsync((char*)l->d_ctx.p + offsetof(DevCtx, pol), &pd, sizeof(pd), hipMemcpyHostToDevice, l->stream));
   HIPCHK(l, hipStreamSynchronize(l->stream));  // `pd` is a stack object
@@ -332,14 +337,19 @@ int muavta_set_pair_policy(MuavtaEnv* e, const MuavtaPairMlp* spec) {
   if (!e) return MUAVTA_E_ARG;
   std::vector<float> w;
   if (spec) {
-    if (spec->hidden != PW_HID || (spec->raw_features != 0 && spec->raw_features != 1) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 || !spec->w2 ||
-        !spec->b2 || !(spec->score_clamp == spec->score_clamp)) {
-      e->err = "muavta_set_pair_policy: bad spec (hidden must be 128, raw_features 0 or 1, six non-null arrays, score_clamp a number)";
+    // raw_features is the MUAVTA_TOK_* kind the network consumes: 0 / 1 an MLP-Pair (hidden 128), MUAVTA_TOK_ESCORT an MLP-Coalition (hidden 256)
+    const bool esc = spec->raw_features == MUAVTA_TOK_ESCORT;
+    if (spec->hidden != (esc ? PWE_HID : PW_HID) || (spec->raw_features != 0 && spec->raw_features != 1 && !esc) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 ||
+        !spec->w2 || !spec->b2 || !(spec->score_clamp == spec->score_clamp)) {
+      e->err = "muavta_set_pair_policy: bad spec (hidden must be 128, raw_features 0 or 1, six non-null arrays, score_clamp a number; "
+               "or raw_features 2 = MUAVTA_TOK_ESCORT, an MLP-Coalition, with hidden 256)";
       return MUAVTA_E_ARG;
     }
-    w = pack_policy<PairLayout>(PW_FLOATS, spec->raw_features ? 20 : 25, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2, [](int k) { return k; });
+    if (esc) w = pack_policy<CoalitionLayout>(PWE_FLOATS, PWE_W0_ROWS, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2, [](int k) { return k; });
+    else w = pack_policy<PairLayout>(PW_FLOATS, spec->raw_features ? 20 : 25, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2, [](int k) { return k; });
   }
-  return install_policy(e, "muavta_set_pair_policy", !spec, POL_PAIR, spec ? spec->raw_features : 0, spec ? spec->score_clamp : 0.f, w);
+  const bool esc = spec && spec->raw_features == MUAVTA_TOK_ESCORT;
+  return install_policy(e, "muavta_set_pair_policy", !spec, esc ? POL_COALITION : POL_PAIR, spec && !esc ? spec->raw_features : 0, spec ? spec->score_clamp : 0.f, w);
 }
 // MLP-ContextPair: the same, with MLPContextPairNet.pair_mlp.  The state_dict's columns are the reference's cat — agent, task, a_pool,
 // t_pool, context; the device's chain takes the env-uniform ones first (a_pool, t_pool, context, agent, task).
@@ -365,7 +375,8 @@ int muavta_pair_scores_device(MuavtaEnv* e, float* scores, float* logits) {
   if (!scores && !logits) return MUAVTA_OK;
   DeviceScope scope_(e->device);
   MAIN_OP(e);
-  if (e->pol_kind == POL_CONTEXT_PAIR) DISPATCH(e, hipLaunchKernelGGL((k_pair_scores<TL, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits))
+  if (e->pol_kind == POL_COALITION) DISPATCH(e, hipLaunchKernelGGL((k_pair_scores<TL, false, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits))
+  else if (e->pol_kind == POL_CONTEXT_PAIR) DISPATCH(e, hipLaunchKernelGGL((k_pair_scores<TL, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits))
   else DISPATCH(e, hipLaunchKernelGGL(k_pair_scores<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits));
   HIPCHK(e, hipGetLastError());
   return MUAVTA_OK;
@@ -375,7 +386,7 @@ int muavta_pair_scores(MuavtaEnv* e, float* scores, float* logits) {
   if (!e->hl.pol_set) { e->err = "muavta_pair_scores: no policy (muavta_set_pair_policy first)"; return MUAVTA_E_STATE; }
   if (!e->did_reset) { e->err = "muavta_pair_scores before reset"; return MUAVTA_E_STATE; }
   DeviceScope scope_(e->device);
-  const size_t one = (size_t)e->n_envs * PS_MA * PS_MT * sizeof(float);
+  const size_t one = (size_t)e->n_envs * PS_MA * (e->pol_kind == POL_COALITION ? PE_MT : PS_MT) * sizeof(float);  // [N, 16, 32], MLP-Coalition: [N, 16, 48]
   if (int rc = grow_staging(e, 2 * one)) return rc;  // (shares the staging buffer of muavta_tokens' host variant)
   float* ds = (float*)e->d_tok.p;
   float* dl = (float*)((char*)e->d_tok.p + one);

@@ -139,12 +139,12 @@ struct ScoredDev {
 // layer 3 and the biases as they are.  See sim/policy.inc.
 struct PairPolicyDev {
   const float* w;    // [PW_FLOATS], null: no policy set
-  float* scratch;    // [N][PS_FLOATS]
+  float* scratch;    // [N][PS_FLOATS] (POL_CONTEXT_PAIR: [N][PSC_FLOATS]; POL_COALITION: [N][PE_FLOATS], a buffer of its own)
   int32_t raw;       // checkpoint's raw_features: tokens of kind MUAVTA_TOK_PAIR_RAW (agent 11 + task 9) instead of MUAVTA_TOK_PAIR (12 + 13)
-  float clamp;       // score_clamp
-  int32_t kind;      // POL_PAIR / POL_CONTEXT_PAIR: which network `w` holds (and which kernel instantiations run it).  Appended: nothing in front of it moves
+  float clamp;       // score_clamp (unused by POL_COALITION: its score is a sigmoid)
+  int32_t kind;      // POL_PAIR / POL_CONTEXT_PAIR / POL_COALITION: which network `w` holds (and which kernel instantiations run it).  Appended: nothing in front of it moves
 };
-enum { POL_PAIR = 0, POL_CONTEXT_PAIR = 1 };
+enum { POL_PAIR = 0, POL_CONTEXT_PAIR = 1, POL_COALITION = 2 };
 enum { PW_HID = 128, PW_W0_ROWS = 25,
        PW_W0 = 0, PW_B0 = PW_W0 + PW_HID * PW_W0_ROWS, PW_W1 = PW_B0 + PW_HID, PW_B1 = PW_W1 + PW_HID * PW_HID, PW_W2 = PW_B1 + PW_HID,
        PW_B2 = PW_W2 + PW_HID, PW_FLOATS = PW_B2 + 16 };
@@ -161,8 +161,21 @@ enum { PC_HID = 192, PC_W0_ROWS = 58,
        PC_W0 = 0, PC_B0 = PC_W0 + PC_HID * PC_W0_ROWS, PC_W1 = PC_B0 + PC_HID, PC_B1 = PC_W1 + PC_HID * PC_HID, PC_W2 = PC_B1 + PC_HID,
        PC_B2 = PC_W2 + PC_HID, PC_FLOATS = PC_B2 + 16 };
 enum { PSC_PRE = PS_FLOATS, PSC_HEAD = PSC_PRE + 36, PSC_FLOATS = PSC_HEAD + PC_HID };
-struct PairLayout { enum { CTX = 0, HID = PW_HID, W0_ROWS = PW_W0_ROWS, W0 = PW_W0, B0 = PW_B0, W1 = PW_W1, B1 = PW_B1, W2 = PW_W2, B2 = PW_B2 }; };
-struct ContextPairLayout { enum { CTX = 1, HID = PC_HID, W0_ROWS = PC_W0_ROWS, W0 = PC_W0, B0 = PC_B0, W1 = PC_W1, B1 = PC_B1, W2 = PC_W2, B2 = PC_B2 }; };
+// MLP-Coalition (muavta_set_pair_policy with raw_features == MUAVTA_TOK_ESCORT): MLPCoalitionNet.pair_mlp, Linear(38, 256) - ReLU - Linear(256, 256) -
+// ReLU - Linear(256, 1) over the escort tokens (agent 16 + task 22 features, 16 x 48 pairs), packed in the same order.  Its per-env scratch
+// block (PE_*, the weights are PWE_*; a buffer of its own, allocated when a policy of this kind is first installed): build_escort_tokens(env, 48, 16) of the plan
+// being made, its scores, and the list of valid cells (768 x u16 — more than the idle LDS in front of Scratch::resid holds on every tile).
+enum { PWE_HID = 256, PWE_W0_ROWS = 38,
+       PWE_W0 = 0, PWE_B0 = PWE_W0 + PWE_HID * PWE_W0_ROWS, PWE_W1 = PWE_B0 + PWE_HID, PWE_B1 = PWE_W1 + PWE_HID * PWE_HID, PWE_W2 = PWE_B1 + PWE_HID,
+       PWE_B2 = PWE_W2 + PWE_HID, PWE_FLOATS = PWE_B2 + 16 };
+enum { PE_MA = 16, PE_MT = 48,
+       PE_TF = 0, PE_AF = PE_TF + PE_MT * 22, PE_EV = PE_AF + PE_MA * 16, PE_SCORES = PE_EV + PE_MA * PE_MT, PE_TID = PE_SCORES + PE_MA * PE_MT,
+       PE_AID = PE_TID + PE_MT, PE_TMASK = PE_AID + PE_MA, PE_AMASK = PE_TMASK + PE_MT / 4, PE_LIST = PE_AMASK + PE_MA / 4,
+       PE_FLOATS = (PE_LIST + PE_MA * PE_MT / 2 + 3) & ~3 };
+// ESC: escort tokens, a 16 x 48 grid, the sigmoid score and the valid-cell list in the env's scratch block
+struct PairLayout { enum { CTX = 0, ESC = 0, HID = PW_HID, W0_ROWS = PW_W0_ROWS, W0 = PW_W0, B0 = PW_B0, W1 = PW_W1, B1 = PW_B1, W2 = PW_W2, B2 = PW_B2 }; };
+struct ContextPairLayout { enum { CTX = 1, ESC = 0, HID = PC_HID, W0_ROWS = PC_W0_ROWS, W0 = PC_W0, B0 = PC_B0, W1 = PC_W1, B1 = PC_B1, W2 = PC_W2, B2 = PC_B2 }; };
+struct CoalitionLayout { enum { CTX = 0, ESC = 1, HID = PWE_HID, W0_ROWS = PWE_W0_ROWS, W0 = PWE_W0, B0 = PWE_B0, W1 = PWE_W1, B1 = PWE_B1, W2 = PWE_W2, B2 = PWE_B2 }; };
 
 template <class TL>
 struct Sim {

@@ -292,7 +292,8 @@ enum { SCORED_EXTRA_LDS = 128 };  // allocate<true>'s task list: one byte per sl
 // BL: the classical baselines (MUAVTA_ALLOC_CAP_GREEDY, MUAVTA_ALLOC_PI; sim/baselines.inc) in instantiations of their own
 // PM: the learned MLP-Pair hybrid (MUAVTA_ALLOC_MLP_PAIR; sim/policy.inc), likewise; launched with SCORED_EXTRA_LDS bytes behind the tile
 // CX (with PM): the installed policy is an MLP-ContextPair (192 wide, pooled rows and the context summary in front of every pair's inputs)
-template <class TL, bool BL = false, bool PM = false, bool CX = false>
+// CO (with PM): the installed policy is an MLP-Coalition (256 wide over the escort tokens, a 16 x 48 grid, sigmoid scores, commit locks)
+template <class TL, bool BL = false, bool PM = false, bool CX = false, bool CO = false>
 __global__ __launch_bounds__(WG) void k_allocate(const DevCtx* __restrict__ ctxp, int interval, int use_vis, int mode,
                                                  int32_t* out_agent, int32_t* out_index, int act_cap, int env_base) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -302,7 +303,8 @@ __global__ __launch_bounds__(WG) void k_allocate(const DevCtx* __restrict__ ctxp
   copy16(L.S, blob, sizeof(EnvState<TL>));
   lds_sync();
   Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, tape_of(ctx, env));
-  if constexpr (PM && CX) sim.template allocate_mlp<true>(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PSC_FLOATS, smem + Lds<TL>::bytes());
+  if constexpr (PM && CO) sim.allocate_coalition(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PE_FLOATS, smem + Lds<TL>::bytes());
+  else if constexpr (PM && CX) sim.template allocate_mlp<true>(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PSC_FLOATS, smem + Lds<TL>::bytes());
   else if constexpr (PM) sim.allocate_mlp(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PS_FLOATS, smem + Lds<TL>::bytes());
   else if constexpr (BL) sim.allocate_baseline(interval, use_vis, mode);
   else sim.allocate(interval, use_vis, mode);
@@ -530,7 +532,7 @@ struct RecordPtrs {
 struct RecBlob { uint32_t w[64]; };  // 256 B: a RecordPtrs<TL> by value
 __global__ void k_store_rec(RecBlob b, uint32_t* dst) { dst[threadIdx.x] = b.w[threadIdx.x]; }
 
-template <class TL, bool REC, bool BL = false, bool PM = false, bool CX = false>
+template <class TL, bool REC, bool BL = false, bool PM = false, bool CX = false, bool CO = false>
 __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned char* lds_own, uint32_t lds_base, int env, int phases, int interval, int use_vis, int mode,
                                                 const RecordPtrs<TL>& rec, int slot, int oslot) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -557,7 +559,9 @@ __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned cha
   }
   lds_sync();
   if (!ABL(9) && (phases & PH_ALLOC) && !(L.S->terminated || L.S->truncated)) {
-    if constexpr (PM && CX) sim.template allocate_mlp<true>(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PSC_FLOATS,
+    if constexpr (PM && CO) sim.allocate_coalition(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PE_FLOATS,
+                                                   reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS);
+    else if constexpr (PM && CX) sim.template allocate_mlp<true>(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PSC_FLOATS,
                                                             reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS);
     else if constexpr (PM) sim.allocate_mlp(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PS_FLOATS,
                                        reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS);
@@ -575,9 +579,10 @@ __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned cha
 }
 
 // (PM: the forward pass keeps a pair's 128 hidden activations in registers, ~145 VGPRs — those instantiations are built for three waves
-// per SIMD, 168 VGPRs, where the tile's other kernels are built for four; CX: 192 activations, two waves per SIMD, 256 VGPRs)
-template <class TL, bool REC, bool BL = false, bool PM = false, bool CX = false>
-__global__ __launch_bounds__(WG, PM ? (TILE_MIN_WAVES(TL) < (CX ? 2 : 3) ? TILE_MIN_WAVES(TL) : (CX ? 2 : 3)) : TILE_MIN_WAVES(TL)) void k_rollout(const DevCtx* __restrict__ ctxp, const uint64_t* seeds, int n_steps, int interval, int use_vis,
+// per SIMD, 168 VGPRs, where the tile's other kernels are built for four; CX: 192 activations, two waves per SIMD, 256 VGPRs;
+// CO: 256 activations, one wave per SIMD — about 480 of the unified 512-entry register file, the allocator's placement, no spill)
+template <class TL, bool REC, bool BL = false, bool PM = false, bool CX = false, bool CO = false>
+__global__ __launch_bounds__(WG, PM ? (CO ? 1 : TILE_MIN_WAVES(TL) < (CX ? 2 : 3) ? TILE_MIN_WAVES(TL) : (CX ? 2 : 3)) : TILE_MIN_WAVES(TL)) void k_rollout(const DevCtx* __restrict__ ctxp, const uint64_t* seeds, int n_steps, int interval, int use_vis,
                                                 int mode, int write_obs, double* metrics, const uint32_t* seedbuf, const RecordPtrs<TL>* __restrict__ recp, int epoch, int env_base) {
   const DevCtx& ctx = ctx_ref(ctxp);
   // The ring pointers of muavta_rollout_record sit in device memory (one slot per handle, written on the launch's stream just ahead of
@@ -670,7 +675,7 @@ static_assert(MUAVTA_PACE_HOLD_POLLS > 0 && MUAVTA_PACE_HOLD_POLLS <= (1 << 16),
       if (threadIdx.x < 16) seen = __hip_atomic_load(pace_row + threadIdx.x, __ATOMIC_RELAXED, MUAVTA_PACE_SCOPE);
     }
 #endif
-    if (ph) rollout_phase<TL, REC, BL, PM, CX>(ctxp, lds_own, lds_base, env, ph, interval, use_vis, mode, rec, k < n_steps ? k : n_steps,
+    if (ph) rollout_phase<TL, REC, BL, PM, CX, CO>(ctxp, lds_own, lds_base, env, ph, interval, use_vis, mode, rec, k < n_steps ? k : n_steps,
                                    (REC && rec.O.tasks && k >= 1 && k <= n_steps) ? k - 1 : -1);
 #if MUAVTA_PACE_PRIO
     if (PACED && k >= 1 && k <= n_steps && (k & (MUAVTA_PACE_EVERY - 1)) == 0) {  // consumed a step later: the load's latency stays off the env's dependent chain
@@ -769,8 +774,8 @@ __global__ __launch_bounds__(WG) void k_tokens(const DevCtx* __restrict__ ctxp, 
 // muavta_pair_scores(_device): the MLP-Pair policy's scores / logits of every env's CURRENT state — build_pair_tokens(env, 32, 16) into
 // the env's scratch block, then the forward pass of sim/policy.inc, the same code the MUAVTA_ALLOC_MLP_PAIR mode runs at a replan.
 // scores / logits: [N, 16, 32] (either may be null); entries whose edge_valid is 0 are written as 0.  The env records are not changed.
-// CX: the installed policy is an MLP-ContextPair.
-template <class TL, bool CX = false>
+// CX: the installed policy is an MLP-ContextPair.  CO: an MLP-Coalition — build_escort_tokens(env, 48, 16), scores / logits [N, 16, 48].
+template <class TL, bool CX = false, bool CO = false>
 __global__ __launch_bounds__(WG) void k_pair_scores(const DevCtx* __restrict__ ctxp, float* scores, float* logits) {
   const DevCtx& ctx = ctx_ref(ctxp);
   const int env = blockIdx.x;
@@ -778,7 +783,13 @@ __global__ __launch_bounds__(WG) void k_pair_scores(const DevCtx* __restrict__ c
   copy16(L.S, blob_of<TL>(ctx, env), sizeof(EnvState<TL>));
   lds_sync();
   Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, nullptr);
-  float* scratch = as_global(ctx.pol.scratch) + (size_t)env * (CX ? PSC_FLOATS : PS_FLOATS);
+  float* scratch = as_global(ctx.pol.scratch) + (size_t)env * (CO ? PE_FLOATS : CX ? PSC_FLOATS : PS_FLOATS);
+  if constexpr (CO) {
+    const size_t at = (size_t)env * PE_MA * PE_MT;
+    sim.coalition_tokens_scratch(scratch);
+    sim.coalition_forward(ctx.pol, scratch, scores ? as_global(scores) + at : nullptr, logits ? as_global(logits) + at : nullptr);
+    return;
+  }
   sim.pair_tokens_scratch(ctx.pol, scratch);
   const size_t at = (size_t)env * PS_MA * PS_MT;
   if constexpr (CX) {

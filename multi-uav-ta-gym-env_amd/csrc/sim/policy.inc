@@ -24,21 +24,28 @@
   // leaves them alone: allocate<true> under MUAVTA_SC_EDGE_VALID_ONLY never reads them).  Scratch: X.cost .. X.spc (the list of valid cells).
   // LY: PairLayout (MLP-Pair, 128 wide) or ContextPairLayout (MLP-ContextPair, 192 wide; `pre`: the env-uniform head of layer 1's input row
   // in the env's scratch block, context_prefix() below, with the 192 floats of PSC_HEAD behind it) — the packed-weight offsets and the width, everything else is the same code.
+  // CoalitionLayout (MLP-Coalition, 256 wide, LY::ESC): escort token rows (agent 16 + task 22 features), a 16 x 48 grid, score = sigmoid of the
+  // logit clipped to +-20, and `glist`: the list of valid cells in the env's scratch block (PE_LIST) — 1,536 B do not fit in front of Scratch::resid.
+  // tpad / apad (LY::ESC): the token builder's task_mask / agent_mask (1 = pad row); a pair of a pad row is masked like one whose edge_valid is 0.
   template <bool RAW, class LY>
-  DEV void pair_forward_t(const PairPolicyDev& pol, const float* tf, const float* af, const float* ev, float* scores, float* logits, bool fill, const float* pre) {
-    constexpr int Da = RAW ? 11 : 12, Dt = RAW ? 9 : 13, NP = LY::CTX ? Da + Dt + (RAW ? 1 : 8) : 0, K0 = NP + Da + Dt, HID = LY::HID, CELLS = PS_MA * PS_MT;
-    static_assert(K0 <= LY::W0_ROWS && HID % 64 == 0, "layer 1's weights are stored k-major, W0_ROWS rows of HID");
+  DEV void pair_forward_t(const PairPolicyDev& pol, const float* tf, const float* af, const float* ev, float* scores, float* logits, bool fill, const float* pre,
+                          uint16_t* glist = nullptr, const uint8_t* tpad = nullptr, const uint8_t* apad = nullptr) {
+    constexpr int Da = LY::ESC ? 16 : RAW ? 11 : 12, Dt = LY::ESC ? 22 : RAW ? 9 : 13, NP = LY::CTX ? Da + Dt + (RAW ? 1 : 8) : 0, K0 = NP + Da + Dt, HID = LY::HID;
+    constexpr int MT = LY::ESC ? (int)PE_MT : (int)PS_MT, CELLS = PS_MA * MT;
+    static_assert(K0 <= LY::W0_ROWS && HID % 64 == 0 && PE_MA == PS_MA, "layer 1's weights are stored k-major, W0_ROWS rows of HID");
     // the list of valid cells: the cost tile and the LSAP's duals / spc behind it (one run of doubles, all idle between the token builder and the plan)
-    static_assert(offsetof(Scratch<TL>, resid) - offsetof(Scratch<TL>, cost) >= CELLS * sizeof(uint16_t) && offsetof(Scratch<TL>, u) > offsetof(Scratch<TL>, cost) &&
-                  offsetof(Scratch<TL>, resid) > offsetof(Scratch<TL>, spc), "the list of valid cells needs 1 KB in front of Scratch::resid");
+    static_assert(LY::ESC || (offsetof(Scratch<TL>, resid) - offsetof(Scratch<TL>, cost) >= CELLS * sizeof(uint16_t) && offsetof(Scratch<TL>, u) > offsetof(Scratch<TL>, cost) &&
+                  offsetof(Scratch<TL>, resid) > offsetof(Scratch<TL>, spc)), "the list of valid cells needs 1 KB in front of Scratch::resid");
     const uint64_t wb = (uint64_t)pol.w;
     uint32_t wlo = __builtin_amdgcn_readfirstlane((uint32_t)wb), whi = __builtin_amdgcn_readfirstlane((uint32_t)(wb >> 32));
     const float clamp = pol.clamp;
-    uint16_t* list = reinterpret_cast<uint16_t*>(X.cost);
+    uint16_t* list;
+    if constexpr (LY::ESC) list = glist; else list = reinterpret_cast<uint16_t*>(X.cost);
     int nv = 0;
     for (int base = 0; base < CELLS; base += WG) {
       const int c = base + lane;
-      const bool v = ev[c] != 0.f;
+      bool v = ev[c] != 0.f;
+      if constexpr (LY::ESC) v = v && tpad[c % MT] == 0 && apad[c / MT] == 0;  // (pad pairs are masked here too, whatever edge_valid holds)
       const unsigned long long m = __ballot(v);
       if (v) list[nv + prefix_count(m)] = (uint16_t)c;
       else if (fill) {
@@ -64,6 +71,7 @@
       }
       cold_sync();  // every lane's outputs are in memory before any lane reads another's
     }
+    if constexpr (LY::ESC) cold_sync();  // the list is in global memory: every lane's entries are there before any lane reads another's
     lds_sync();
     for (int b0 = 0; b0 < nv; b0 += WG) {  // (uniform)
       // (the weights' base is made opaque once per pass: otherwise layer 1's 128 biases — pass-invariant scalar loads — are hoisted in
@@ -72,7 +80,7 @@
       pol_cf* w = (pol_cf*)(((uint64_t)whi << 32) | (uint64_t)wlo);
       const bool act = b0 + lane < nv;
       const int c = list[act ? b0 + lane : b0];  // lanes beyond the list redo the pass's first pair; their result is dropped
-      const int i = c / PS_MT, j = c - i * PS_MT;
+      const int i = c / MT, j = c - i * MT;
       const float* xa = af + i * Da;
       const float* xt = tf + j * Dt;
       // The arithmetic is written two chains wide (v_pk_fma_f32: two independent IEEE fmas per instruction, each chain's own
@@ -97,6 +105,12 @@
         }
 #pragma unroll
         for (int t = 0; t < 32; t++) h1[nc + t] = pol_f2{pol_relu(h1[nc + t].x), pol_relu(h1[nc + t].y)};
+        if constexpr (HID > 192) {  // (the upper half is made opaque as soon as it is complete, as layer 2 does below: see there)
+          if (nc >= 64) {
+#pragma unroll
+            for (int t = 0; t < 32; t++) asm volatile("" : "+v"(h1[nc + t]));
+          }
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
       // Layers 2 and 3 together: four of layer 2's chains side by side (outputs n .. n + 3, their weights interleaved in memory so
@@ -110,6 +124,10 @@
         pol_cf* r = w + LY::W1 + n * HID;  // [k][4]
         // (no instruction: the activations become new values in every iteration, so the (h, h) operand pairs below are formed where
         // they are used — as the packed FMA's operand select — instead of once in front of the loop in 128 more register pairs)
+        // (256 wide: the kernel is built for one wave per SIMD, so the 256 activations live in the unified 512-entry register file — the
+        // allocator places them (about 480 registers in all, nothing spilled) and moves what it keeps in the accumulator half where the
+        // products need it.  Pinning the upper half there by hand ("a" constraints) measured 2 - 8 % slower and left scratch reloads in
+        // this loop; the upper half in LDS 32 % slower: DESIGN.md §7.1.)
 #pragma unroll
         for (int q = 0; q < HID / 2; q++) asm volatile("" : "+v"(h1[q]));
         pol_f2 a01 = pol_f2{w[LY::B1 + n], w[LY::B1 + n + 1]}, a23 = pol_f2{w[LY::B1 + n + 2], w[LY::B1 + n + 3]};
@@ -118,8 +136,14 @@
         for (int q = 0; q < 32; q++) cw[q] = r[q];
 #pragma unroll
         for (int kc = 0; kc < HID; kc += 8) {
+          pol_f2 hh[4];
+#pragma unroll
+          for (int p = 0; p < 4; p++) {
+            hh[p] = h1[kc / 2 + p];
+            if (HID > 192 && kc >= 128) asm volatile("" : "+v"(hh[p]));  // (256 wide: the upper half's copy is made here, in its chunk, not at the top of the loop)
+          }
           {
-            const float h = h1[kc / 2].x;
+            const float h = hh[0].x;
             a01 = __builtin_elementwise_fma(pol_f2{cw[0], cw[1]}, pol_f2{h, h}, a01);
             a23 = __builtin_elementwise_fma(pol_f2{cw[2], cw[3]}, pol_f2{h, h}, a23);
           }
@@ -131,7 +155,7 @@
           }
 #pragma unroll
           for (int q = 1; q < 8; q++) {
-            const float h = (q & 1) ? h1[(kc + q) / 2].y : h1[(kc + q) / 2].x;
+            const float h = (q & 1) ? hh[q / 2].y : hh[q / 2].x;
             a01 = __builtin_elementwise_fma(pol_f2{cw[4 * q], cw[4 * q + 1]}, pol_f2{h, h}, a01);
             a23 = __builtin_elementwise_fma(pol_f2{cw[4 * q + 2], cw[4 * q + 3]}, pol_f2{h, h}, a23);
           }
@@ -148,7 +172,9 @@
       }
       if (act) {
         if (logits) logits[c] = logit;
-        if (scores) scores[c] = tanhf(logit) * clamp;
+        if constexpr (LY::ESC) {  // AttentionEscort.act: 1 / (1 + exp(-clip(logit, -20, 20))), float32, IEEE division
+          if (scores) scores[c] = 1.0f / (1.0f + expf(-fminf(fmaxf(logit, -20.0f), 20.0f)));
+        } else if (scores) scores[c] = tanhf(logit) * clamp;
       }
     }
     lds_sync();
@@ -193,6 +219,42 @@
   DEV void context_pair_forward(const PairPolicyDev& pol, const float* base, float* scores, float* logits, bool fill) {
     if (pol.raw) pair_forward_t<true, ContextPairLayout>(pol, base + PS_TF, base + PS_AF, base + PS_EV, scores, logits, fill, base + PSC_PRE);  // (uniform)
     else pair_forward_t<false, ContextPairLayout>(pol, base + PS_TF, base + PS_AF, base + PS_EV, scores, logits, fill, base + PSC_PRE);
+  }
+  // ---- MLP-Coalition: AttentionEscort(use_attention=False) (TaskAllocation/Hybrid/AttentionEscort.py:326-367,370-524) ---------------------------
+  //   logits = pair_mlp(cat([agent_feats[i], task_feats[j]]))      Linear(38, 256) - ReLU - Linear(256, 256) - ReLU - Linear(256, 1)
+  //   scores = sigmoid(clip(logits, -20, 20)) * edge_valid * non-pad -> _plan_from_scores: allocate_tasks(force=True, reserved=committed_names,
+  //   edge_scores = every non-pad pair) + apply_agent_commits.  CONTRACT (DESIGN.md §7.1; tests/coalition_mlp_py.py): layer 1 is one chain over the
+  //   agent row's 16 features, then the task row's 22; layers 2 and 3 as above; score = 1.0f / (1.0f + expf(-fminf(fmaxf(logit, -20.0f), 20.0f)));
+  //   pad pairs and pairs whose edge_valid is 0 are not evaluated and score 0; score_clamp is not used.
+  // build_escort_tokens(env, 48, 16) of the current state into this env's PE_FLOATS block
+  DEV void coalition_tokens_scratch(float* base) {
+    TokPtrs K;
+    K.task_feats = base + PE_TF; K.agent_feats = base + PE_AF; K.edge_valid = base + PE_EV;
+    K.task_ids = reinterpret_cast<int32_t*>(base + PE_TID); K.agent_ids = reinterpret_cast<int32_t*>(base + PE_AID);
+    K.task_mask = reinterpret_cast<uint8_t*>(base + PE_TMASK); K.agent_mask = reinterpret_cast<uint8_t*>(base + PE_AMASK);
+    K.n_urgent = nullptr; K.expert_mask = nullptr; K.replanned = nullptr;
+    K.kind = MUAVTA_TOK_ESCORT; K.max_tasks = PE_MT; K.max_agents = PE_MA;
+    cold_sync();  // the token rows read currentReqs / allocatedReqs
+    tokens(K, 0);
+    cold_sync();  // every lane's rows are in memory before any lane reads another's
+  }
+  // masked cells are always written as 0: the plan below reads every non-pad cell (no MUAVTA_SC_EDGE_VALID_ONLY), and the reference's score there is 0
+  DEV void coalition_forward(const PairPolicyDev& pol, float* base, float* scores, float* logits) {
+    pair_forward_t<false, CoalitionLayout>(pol, base + PE_TF, base + PE_AF, base + PE_EV, scores, logits, true, nullptr, reinterpret_cast<uint16_t*>(base + PE_LIST),
+                                           reinterpret_cast<const uint8_t*>(base + PE_TMASK), reinterpret_cast<const uint8_t*>(base + PE_AMASK));
+  }
+  // MUAVTA_ALLOC_MLP_PAIR with a POL_COALITION policy: run_escort_episode's MLP-Coalition branch (experiments/escort_eval.py:181-188) —
+  //     if _should_replan(env, events, interval):  result, *_ = mlp.plan(env, hung_force, events=events, explore=False, force=True)
+  DEV void allocate_coalition(int interval, int use_visibility, const PairPolicyDev& pol, float* scratch, uint8_t* sc_list) {
+    if (gate_fires(MUAVTA_GATE_ESCORT, interval)) {
+      coalition_tokens_scratch(scratch);
+      coalition_forward(pol, scratch, scratch + PE_SCORES, nullptr);
+      cold_sync();  // the scores are in memory before the cost evaluation reads them across lanes
+    }
+    ScoredDev sc;
+    sc.scores = scratch + PE_SCORES; sc.pri = nullptr; sc.reserved = nullptr; sc.selected = nullptr; sc.replanned = nullptr;
+    sc.kind = MUAVTA_TOK_ESCORT; sc.MT = PE_MT; sc.MA = PE_MA; sc.gate = MUAVTA_GATE_ESCORT; sc.flags = MUAVTA_SC_COMMIT;
+    allocate<true>(interval, use_visibility, 4, &sc, 0, sc_list);
   }
   // build_pair_tokens(env, 32, 16[, raw]) of the current state into this env's scratch block
   DEV void pair_tokens_scratch(const PairPolicyDev& pol, float* base) {

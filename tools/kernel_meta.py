@@ -10,9 +10,9 @@ import tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-# names of the bool template arguments behind the tile (k_rollout<TL, REC, BL, PM, CX>, k_allocate<TL, BL, PM, CX>, k_pair_scores<TL, CX>;
-# BL = the baseline allocators, PM = the learned pair policy, CX = that policy is an MLP-ContextPair)
-FLAGS = {"k_rollout": ("REC", "BL", "PM", "CX"), "k_allocate": ("BL", "PM", "CX"), "k_pair_scores": ("CX",)}
+# names of the bool template arguments behind the tile (k_rollout<TL, REC, BL, PM, CX, CO>, k_allocate<TL, BL, PM, CX, CO>, k_pair_scores<TL, CX, CO>;
+# BL = the baseline allocators, PM = the learned pair policy, CX = that policy is an MLP-ContextPair, CO = it is an MLP-Coalition)
+FLAGS = {"k_rollout": ("REC", "BL", "PM", "CX", "CO"), "k_allocate": ("BL", "PM", "CX", "CO"), "k_pair_scores": ("CX", "CO")}
 
 
 def short(name):
