@@ -83,7 +83,7 @@ struct MuavtaEnv {
   DevBuf<void> d_comm;    // [64 f64 send | 64 x n_ranks f64 recv | 64 i64 send | 64 i64 recv]
   DevBuf<double> d_metrics;
   DevBuf<float> d_pol_w, d_pol_scratch;  // muavta_set_pair_policy: this lane's copy of the packed weights, its per-env token / score scratch
-  DevBuf<float> d_pol_scratch_e;         // ... and the larger one of the MLP-Coalition kind ([N][PE_FLOATS]), allocated when such a policy first reaches the lane
+  DevBuf<float> d_pol_scratch_e;         // ... and the larger one of the MLP-Coalition kind ([N][PolCoalition::FLOATS]), allocated when such a policy first reaches the lane
   int pol_kind = POL_PAIR;               // ... and which network they hold (push_policy): selects the kernel instantiation of MUAVTA_ALLOC_MLP_PAIR on this lane
   ObsPtrs O{};  // the observation buffers as the kernels see them: views of obs_mem
   DevBuf<void> obs_mem[7];
@@ -128,7 +128,7 @@ struct MuavtaEnv {
     unsigned long long ring_no[RING] = {};      // ... as that lane's launch number
     unsigned long long n_launches = 0;
     std::vector<hipEvent_t> pending_waits;  // muavta_wait_stream events recorded while there was no second lane: one created later waits on them
-    // muavta_set_pair_policy / muavta_set_context_pair_policy: the ONE installed policy — its packed weights (PW_* / PC_* / PWE_* layout by pol_kind) as the
+    // muavta_set_pair_policy / muavta_set_context_pair_policy: the ONE installed policy — its packed weights (the W layout of pol_kind's traits) as the
     // caller last set them; a second lane created later gets its copy from here
     std::vector<float> pol_w;
     int pol_kind = POL_PAIR;
@@ -148,24 +148,45 @@ static int create_lane(const MuavtaParams* params, int32_t n_envs, int32_t devic
 
 namespace {
 
+// THE mapping from a lane's allocator mode and installed policy kind to the tag types that name its kernel instantiations: f is called with
+// a value of the one tag (traits) type that applies, and its result is returned.  for_each_policy: f with every learned policy's traits.
+// Where a kernel template is first named decides where the compiler emits the kernel, and that order is kept (it is why the mapping tests
+// the kinds from the last to the first, and why it returns `auto`: a function with a deduced return type is instantiated where it is
+// first called, so the kernels named through it stay where the hand-written selections it replaces had them).
+template <class F>
+auto with_policy(int kind, F f) {
+  switch (kind) {
+    case POL_COALITION: return f(PolCoalition{});
+    case POL_CONTEXT_PAIR: return f(PolContextPair{});
+    default: return f(PolPair{});
+  }
+}
+template <class F>
+auto with_allocator(const MuavtaEnv* e, F f) {
+  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) return with_policy(e->pol_kind, [&](auto pol) { return f(AllocLearned<decltype(pol)>{}); });
+  if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) return f(AllocBaseline{});
+  return f(AllocHungarian{});
+}
+template <class F>
+void for_each_policy(F f) { f(PolPair{}); f(PolContextPair{}); f(PolCoalition{}); }
+
+// Tiles whose LDS image exceeds the default limit: every kernel launched with dynamic LDS is allowed the tile's bytes, plus what its
+// allocator tag needs behind the tile.  (Named in the order the kernels are emitted in, see above.)
 template <class TL>
 int launch_attr(MuavtaEnv* e) {
-  size_t lds = Lds<TL>::bytes();
+  const size_t lds = Lds<TL>::bytes();
   e->lds_bytes = lds;
-  if (lds > 48 * 1024) {
-    const void* ks[] = {reinterpret_cast<const void*>(&k_reset<TL>), reinterpret_cast<const void*>(&k_step<TL>), reinterpret_cast<const void*>(&k_allocate<TL>),
-                        reinterpret_cast<const void*>(&k_rollout<TL, false>), reinterpret_cast<const void*>(&k_rollout<TL, true>), reinterpret_cast<const void*>(&k_metrics<TL>), reinterpret_cast<const void*>(&k_observe<TL>),
-                        reinterpret_cast<const void*>(&k_tokens<TL>), reinterpret_cast<const void*>(&k_call<TL>), reinterpret_cast<const void*>(&k_context<TL>),
-                        reinterpret_cast<const void*>(&k_allocate<TL, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, true>),
-                        reinterpret_cast<const void*>(&k_pair_scores<TL>), reinterpret_cast<const void*>(&k_rollout<TL, false, false, true>),
-                        reinterpret_cast<const void*>(&k_pair_scores<TL, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, false, true, true>),
-                        reinterpret_cast<const void*>(&k_pair_scores<TL, false, true>), reinterpret_cast<const void*>(&k_rollout<TL, false, false, true, false, true>)};
-    for (const void* k : ks) HIPCHK(e, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate<TL, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate<TL, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate<TL, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_allocate_scored<TL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + SCORED_EXTRA_LDS));
-  }
+  std::vector<std::pair<const void*, size_t>> ks;  // kernel, bytes behind the tile
+  const auto allow = [&](auto* kernel, size_t extra) { ks.emplace_back(reinterpret_cast<const void*>(kernel), extra); };
+  const auto allocator = [&](auto al) { allow(&k_allocate<TL, decltype(al)>, al.EXTRA_LDS); allow(&k_rollout<TL, false, decltype(al)>, 0); };
+  allow(&k_reset<TL>, 0); allow(&k_step<TL>, 0);
+  allocator(AllocHungarian{});
+  allow(&k_rollout<TL, true, AllocHungarian>, 0); allow(&k_metrics<TL>, 0); allow(&k_observe<TL>, 0); allow(&k_tokens<TL>, 0); allow(&k_call<TL>, 0); allow(&k_context<TL>, 0);
+  allocator(AllocBaseline{});
+  for_each_policy([&](auto pol) { allow(&k_pair_scores<TL, decltype(pol)>, 0); allocator(AllocLearned<decltype(pol)>{}); });
+  allow(&k_allocate_scored<TL>, SCORED_EXTRA_LDS);
+  if (lds > 48 * 1024)
+    for (const auto& k : ks) HIPCHK(e, hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + k.second)));
   return MUAVTA_OK;
 }
 

@@ -27,22 +27,13 @@ TokOut record_tokens(const MuavtaRecord& r) {
   return {r.task_feats, r.task_mask, r.task_ids, r.agent_feats, r.agent_mask, r.agent_ids, r.edge_valid, r.n_urgent, r.expert_mask, r.replanned};
 }
 
-// The instantiation of a kernel family that an allocator mode runs (one signature per family) and the dynamic LDS it is launched with;
-// launch_attr names every one of them.  (allocate_kernel is a plain function in front of its caller: where a kernel template is first
-// named decides the order in which the compiler emits the kernels, and that order is kept.)
+// The instantiation of a kernel family that the lane's allocator runs (one signature per family; with_allocator picks the tag) and the
+// dynamic LDS it is launched with; launch_attr names every one of them.  (allocate_kernel is a plain function in front of its caller:
+// where a kernel template is first named decides the order in which the compiler emits the kernels, and that order is kept.)
 typedef void (*AllocateFn)(const DevCtx*, int, int, int, int32_t*, int32_t*, int, int);
 struct AllocateKernel { AllocateFn fn; size_t lds; };
 template <class TL>
 using RolloutFn = void (*)(const DevCtx*, const uint64_t*, int, int, int, int, int, double*, const uint32_t*, const RecordPtrs<TL>*, int, int);
-template <class TL>
-RolloutFn<TL> rollout_kernel(bool recording, int alloc_mode, int pol_kind) {  // (muavta_rollout_record refuses the modes past the Hungarian family)
-  if (recording) return &k_rollout<TL, true>;
-  if (alloc_mode == MUAVTA_ALLOC_MLP_PAIR && pol_kind == POL_COALITION) return &k_rollout<TL, false, false, true, false, true>;
-  if (alloc_mode == MUAVTA_ALLOC_MLP_PAIR && pol_kind == POL_CONTEXT_PAIR) return &k_rollout<TL, false, false, true, true>;
-  if (alloc_mode == MUAVTA_ALLOC_MLP_PAIR) return &k_rollout<TL, false, false, true>;
-  if (alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) return &k_rollout<TL, false, true>;
-  return &k_rollout<TL, false>;
-}
 
 template <class TL>
 static void launch_tokens(MuavtaEnv* e, const TokOut& out, int kind, int max_tasks, int max_agents) {
@@ -94,7 +85,8 @@ static void launch_rollout(MuavtaEnv* e, const Target& t, const uint64_t* ds, in
     slot += MuavtaEnv::REC_SLOT;  // slot 1: the RecordPtrs of this launch
     hipLaunchKernelGGL(k_store_rec, dim3(1), dim3(64), 0, t.stream, blob, (uint32_t*)slot);
   }
-  const RolloutFn<TL> fn = rollout_kernel<TL>(rec != nullptr, e->alloc_mode, e->pol_kind);
+  const RolloutFn<TL> fn = rec ? &k_rollout<TL, true, AllocHungarian>  // (muavta_rollout_record refuses the modes past the Hungarian family)
+                               : with_allocator(e, [](auto al) -> RolloutFn<TL> { return &k_rollout<TL, false, decltype(al)>; });
   hipLaunchKernelGGL(fn, dim3(t.count), dim3(WG), extra_lds, t.stream, (const DevCtx*)e->d_ctx, ds, n_steps, interval, use_vis, e->alloc_mode, write_obs,
                      (double*)e->d_metrics, sb, (const RecordPtrs<TL>*)slot, epoch, t.first);
 }
@@ -210,13 +202,11 @@ int muavta_step_part(MuavtaEnv* e, int32_t part, const int32_t* act_agent, const
 }
 
 static AllocateKernel allocate_kernel(MuavtaEnv* e) {
-  AllocateKernel k{};
-  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR && e->pol_kind == POL_COALITION) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true, false, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
-  else if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR && e->pol_kind == POL_CONTEXT_PAIR) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
-  else if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, false, true>, Lds<TL>::bytes() + SCORED_EXTRA_LDS}))
-  else if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, true>, Lds<TL>::bytes()}))
-  else DISPATCH(e, (k = AllocateKernel{&k_allocate<TL>, Lds<TL>::bytes()}));
-  return k;
+  return with_allocator(e, [e](auto al) {
+    AllocateKernel k{};
+    DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, decltype(al)>, Lds<TL>::bytes() + al.EXTRA_LDS}));
+    return k;
+  });
 }
 // The planner of the handle's allocator mode for the whole batch or a part: the plan is staged in the env records and, as action rows, in
 // the target's staging pair; act_* (both or neither) receive the target's rows and make the call wait.

@@ -254,17 +254,19 @@ static int push_policy(MuavtaEnv* l, const MuavtaEnv::HandleLevel& hl) {
   MAIN_OP(l);
   PairPolicyDev pd;
   memset(&pd, 0, sizeof(pd));
-  const size_t w_floats = PWE_FLOATS;
-  static_assert(PWE_FLOATS >= PC_FLOATS && PWE_FLOATS >= PW_FLOATS, "the lane's weight buffer holds the largest kind");
+  // the lane's weight buffer holds the largest kind; MLP-Pair and MLP-ContextPair share the scratch buffer of the larger block
+  const size_t w_floats = PolCoalition::W::FLOATS, s_floats = PolContextPair::FLOATS, se_floats = PolCoalition::FLOATS;
+  static_assert(PolCoalition::W::FLOATS >= PolContextPair::W::FLOATS && PolCoalition::W::FLOATS >= PolPair::W::FLOATS && PolContextPair::FLOATS >= PolPair::FLOATS,
+                "buffer sizes");
   if (hl.pol_set) {
     if (!l->d_pol_w) HIPCHK(l, l->d_pol_w.alloc(w_floats * sizeof(float)));
     if (!l->d_pol_scratch) {
-      HIPCHK(l, l->d_pol_scratch.alloc((size_t)l->n_envs * PSC_FLOATS * sizeof(float)));
-      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch, 0, (size_t)l->n_envs * PSC_FLOATS * sizeof(float), l->stream));
+      HIPCHK(l, l->d_pol_scratch.alloc((size_t)l->n_envs * s_floats * sizeof(float)));
+      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch, 0, (size_t)l->n_envs * s_floats * sizeof(float), l->stream));
     }
     if (hl.pol_kind == POL_COALITION && !l->d_pol_scratch_e) {  // the escort-token block: only lanes that run this kind pay for it
-      HIPCHK(l, l->d_pol_scratch_e.alloc((size_t)l->n_envs * PE_FLOATS * sizeof(float)));
-      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch_e, 0, (size_t)l->n_envs * PE_FLOATS * sizeof(float), l->stream));
+      HIPCHK(l, l->d_pol_scratch_e.alloc((size_t)l->n_envs * se_floats * sizeof(float)));
+      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch_e, 0, (size_t)l->n_envs * se_floats * sizeof(float), l->stream));
     }
     if (hl.pol_w.size() > w_floats) { l->err = "push_policy: packed weights larger than the lane's buffer"; return MUAVTA_E_ARG; }
     HIPCHK(l, hipMemcpyAsync(l->d_pol_w, hl.pol_w.data(), hl.pol_w.size() * sizeof(float), hipMemcpyHostToDevice, l->stream));
@@ -314,11 +316,12 @@ static int install_policy(MuavtaEnv* e, const char* who, bool clear, int kind, i
   return rc;
 }
 
-// state_dict layout -> the device's: layer 1 k-major with device row k taken from column col0(k); layer 2 in groups of four interleaved outputs
-template <class LY, class Col0>
-static std::vector<float> pack_policy(size_t floats, int k0, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2, const float* b2, Col0 col0) {
-  const int H = LY::HID;
-  std::vector<float> w(floats, 0.f);
+// state_dict layout -> the device's (POL::W): layer 1 k-major with device row k taken from column col0(k); layer 2 in groups of four interleaved outputs
+template <class POL, class Col0>
+static std::vector<float> pack_policy(bool raw, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2, const float* b2, Col0 col0) {
+  typedef typename POL::W LY;
+  const int H = LY::HID, k0 = POL::np(raw) + POL::da(raw) + POL::dt(raw);
+  std::vector<float> w(LY::FLOATS, 0.f);
   for (int n = 0; n < H; n++)
     for (int k = 0; k < k0; k++) w[LY::W0 + (size_t)k * H + n] = w0[(size_t)n * k0 + col0(k)];  // k-major on the device
   memcpy(&w[LY::B0], b0, H * sizeof(float));
@@ -339,14 +342,14 @@ int muavta_set_pair_policy(MuavtaEnv* e, const MuavtaPairMlp* spec) {
   if (spec) {
     // raw_features is the MUAVTA_TOK_* kind the network consumes: 0 / 1 an MLP-Pair (hidden 128), MUAVTA_TOK_ESCORT an MLP-Coalition (hidden 256)
     const bool esc = spec->raw_features == MUAVTA_TOK_ESCORT;
-    if (spec->hidden != (esc ? PWE_HID : PW_HID) || (spec->raw_features != 0 && spec->raw_features != 1 && !esc) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 ||
+    if (spec->hidden != (esc ? PolCoalition::W::HID : PolPair::W::HID) || (spec->raw_features != 0 && spec->raw_features != 1 && !esc) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 ||
         !spec->w2 || !spec->b2 || !(spec->score_clamp == spec->score_clamp)) {
       e->err = "muavta_set_pair_policy: bad spec (hidden must be 128, raw_features 0 or 1, six non-null arrays, score_clamp a number; "
                "or raw_features 2 = MUAVTA_TOK_ESCORT, an MLP-Coalition, with hidden 256)";
       return MUAVTA_E_ARG;
     }
-    if (esc) w = pack_policy<CoalitionLayout>(PWE_FLOATS, PWE_W0_ROWS, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2, [](int k) { return k; });
-    else w = pack_policy<PairLayout>(PW_FLOATS, spec->raw_features ? 20 : 25, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2, [](int k) { return k; });
+    if (esc) w = pack_policy<PolCoalition>(false, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2, [](int k) { return k; });
+    else w = pack_policy<PolPair>(spec->raw_features != 0, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2, [](int k) { return k; });
   }
   const bool esc = spec && spec->raw_features == MUAVTA_TOK_ESCORT;
   return install_policy(e, "muavta_set_pair_policy", !spec, esc ? POL_COALITION : POL_PAIR, spec && !esc ? spec->raw_features : 0, spec ? spec->score_clamp : 0.f, w);
@@ -357,14 +360,14 @@ int muavta_set_context_pair_policy(MuavtaEnv* e, const MuavtaContextPairMlp* spe
   if (!e) return MUAVTA_E_ARG;
   std::vector<float> w;
   if (spec) {
-    if (spec->hidden != PC_HID || (spec->raw_features != 0 && spec->raw_features != 1) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 || !spec->w2 ||
+    if (spec->hidden != PolContextPair::W::HID || (spec->raw_features != 0 && spec->raw_features != 1) || !spec->w0 || !spec->b0 || !spec->w1 || !spec->b1 || !spec->w2 ||
         !spec->b2 || !(spec->score_clamp == spec->score_clamp)) {
       e->err = "muavta_set_context_pair_policy: bad spec (hidden must be 192, raw_features 0 or 1, six non-null arrays, score_clamp a number)";
       return MUAVTA_E_ARG;
     }
-    const int pairw = spec->raw_features ? 20 : 25, np = pairw + (spec->raw_features ? 1 : 8);  // agent + task columns; a_pool + t_pool + context columns
-    w = pack_policy<ContextPairLayout>(PC_FLOATS, pairw + np, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2,
-                                       [=](int k) { return k < np ? k + pairw : k - np; });
+    const bool raw = spec->raw_features != 0;
+    const int pairw = PolContextPair::da(raw) + PolContextPair::dt(raw), np = PolContextPair::np(raw);  // agent + task columns; a_pool + t_pool + context columns
+    w = pack_policy<PolContextPair>(raw, spec->w0, spec->b0, spec->w1, spec->b1, spec->w2, spec->b2, [=](int k) { return k < np ? k + pairw : k - np; });
   }
   return install_policy(e, "muavta_set_context_pair_policy", !spec, POL_CONTEXT_PAIR, spec ? spec->raw_features : 0, spec ? spec->score_clamp : 0.f, w);
 }
@@ -375,9 +378,9 @@ int muavta_pair_scores_device(MuavtaEnv* e, float* scores, float* logits) {
   if (!scores && !logits) return MUAVTA_OK;
   DeviceScope scope_(e->device);
   MAIN_OP(e);
-  if (e->pol_kind == POL_COALITION) DISPATCH(e, hipLaunchKernelGGL((k_pair_scores<TL, false, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits))
-  else if (e->pol_kind == POL_CONTEXT_PAIR) DISPATCH(e, hipLaunchKernelGGL((k_pair_scores<TL, true>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits))
-  else DISPATCH(e, hipLaunchKernelGGL(k_pair_scores<TL>, dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits));
+  with_policy(e->pol_kind, [&](auto pol) {
+    DISPATCH(e, hipLaunchKernelGGL((k_pair_scores<TL, decltype(pol)>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits));
+  });
   HIPCHK(e, hipGetLastError());
   return MUAVTA_OK;
 }
@@ -386,7 +389,7 @@ int muavta_pair_scores(MuavtaEnv* e, float* scores, float* logits) {
   if (!e->hl.pol_set) { e->err = "muavta_pair_scores: no policy (muavta_set_pair_policy first)"; return MUAVTA_E_STATE; }
   if (!e->did_reset) { e->err = "muavta_pair_scores before reset"; return MUAVTA_E_STATE; }
   DeviceScope scope_(e->device);
-  const size_t one = (size_t)e->n_envs * PS_MA * (e->pol_kind == POL_COALITION ? PE_MT : PS_MT) * sizeof(float);  // [N, 16, 32], MLP-Coalition: [N, 16, 48]
+  const size_t one = with_policy(e->pol_kind, [e](auto pol) { typedef typename decltype(pol)::Blk B; return (size_t)e->n_envs * B::MA * B::MT * sizeof(float); });  // [N, 16, 32], MLP-Coalition: [N, 16, 48]
   if (int rc = grow_staging(e, 2 * one)) return rc;  // (shares the staging buffer of muavta_tokens' host variant)
   float* ds = (float*)e->d_tok.p;
   float* dl = (float*)((char*)e->d_tok.p + one);

@@ -138,44 +138,75 @@ struct ScoredDev {
 // their weights interleaved ([n / 4][k][n % 4]: the four chains that run side by side read one k of each from neighbouring words);
 // layer 3 and the biases as they are.  See sim/policy.inc.
 struct PairPolicyDev {
-  const float* w;    // [PW_FLOATS], null: no policy set
-  float* scratch;    // [N][PS_FLOATS] (POL_CONTEXT_PAIR: [N][PSC_FLOATS]; POL_COALITION: [N][PE_FLOATS], a buffer of its own)
+  const float* w;    // [POL::W::FLOATS] of the installed kind, null: no policy set
+  float* scratch;    // [N][POL::FLOATS] (POL_COALITION: a buffer of its own)
   int32_t raw;       // checkpoint's raw_features: tokens of kind MUAVTA_TOK_PAIR_RAW (agent 11 + task 9) instead of MUAVTA_TOK_PAIR (12 + 13)
   float clamp;       // score_clamp (unused by POL_COALITION: its score is a sigmoid)
   int32_t kind;      // POL_PAIR / POL_CONTEXT_PAIR / POL_COALITION: which network `w` holds (and which kernel instantiations run it).  Appended: nothing in front of it moves
 };
 enum { POL_PAIR = 0, POL_CONTEXT_PAIR = 1, POL_COALITION = 2 };
-enum { PW_HID = 128, PW_W0_ROWS = 25,
-       PW_W0 = 0, PW_B0 = PW_W0 + PW_HID * PW_W0_ROWS, PW_W1 = PW_B0 + PW_HID, PW_B1 = PW_W1 + PW_HID * PW_HID, PW_W2 = PW_B1 + PW_HID,
-       PW_B2 = PW_W2 + PW_HID, PW_FLOATS = PW_B2 + 16 };
-// per-env scratch, in floats: the token tensors build_pair_tokens(env, 32, 16) of the plan being made, and its scores
-enum { PS_MA = 16, PS_MT = 32,
-       PS_TF = 0, PS_AF = PS_TF + PS_MT * 13, PS_EV = PS_AF + PS_MA * 12, PS_SCORES = PS_EV + PS_MA * PS_MT, PS_TID = PS_SCORES + PS_MA * PS_MT,
-       PS_AID = PS_TID + PS_MT, PS_TMASK = PS_AID + PS_MA, PS_AMASK = PS_TMASK + PS_MT / 4, PS_FLOATS = (PS_AMASK + PS_MA / 4 + 3) & ~3 };
-// muavta_set_context_pair_policy: MLPContextPairNet.pair_mlp, Linear(58|41, 192) - ReLU - Linear(192, 192) - ReLU - Linear(192, 1).  A packed-weight
-// layout of its own, in the same order (layer 1 k-major with its columns permuted to a_pool, t_pool, context, agent, task; layer 2 in
-// groups of four interleaved outputs), and a larger per-env scratch block: the MLP-Pair block, then the env-uniform head of layer 1's
-// input row — a_pool [12|11], t_pool [13|9], context [8|1], contiguous (PSC_PRE; sim/policy.inc: context_prefix) — and the 192 chains' values
-// after those inputs (PSC_HEAD: computed once per plan, every pair's chain continues from them).
-enum { PC_HID = 192, PC_W0_ROWS = 58,
-       PC_W0 = 0, PC_B0 = PC_W0 + PC_HID * PC_W0_ROWS, PC_W1 = PC_B0 + PC_HID, PC_B1 = PC_W1 + PC_HID * PC_HID, PC_W2 = PC_B1 + PC_HID,
-       PC_B2 = PC_W2 + PC_HID, PC_FLOATS = PC_B2 + 16 };
-enum { PSC_PRE = PS_FLOATS, PSC_HEAD = PSC_PRE + 36, PSC_FLOATS = PSC_HEAD + PC_HID };
+// The packed weights of a three-layer MLP of width HID whose first layer takes up to W0_ROWS inputs (k-major), in floats.
+template <int HID_, int W0_ROWS_>
+struct PackedMlp {
+  enum { HID = HID_, W0_ROWS = W0_ROWS_,
+         W0 = 0, B0 = W0 + HID * W0_ROWS, W1 = B0 + HID, B1 = W1 + HID * HID, W2 = B1 + HID, B2 = W2 + HID, FLOATS = B2 + 16 };
+};
+// The front of a policy's per-env scratch block, in floats: the token tensors of the plan being made — MT task rows of DT features, 16
+// agent rows of DA — and its scores.  END: the first float behind the pad masks; what follows belongs to the policy's traits.
+template <int MT_, int DT, int DA>
+struct TokenBlock {
+  enum { MA = 16, MT = MT_,
+         TF = 0, AF = TF + MT * DT, EV = AF + MA * DA, SCORES = EV + MA * MT, TID = SCORES + MA * MT,
+         AID = TID + MT, TMASK = AID + MA, AMASK = TMASK + MT / 4, END = AMASK + MA / 4 };
+};
+// One traits type per learned network: everything sim/policy.inc, the kernels and the host layer need to know about it.
+//   KIND, W             the POL_* kind and the packed-weight layout
+//   Blk, FLOATS         the token block and the per-env stride of the scratch buffer (grid: Blk::MA x Blk::MT)
+//   tok_kind(raw)       the MUAVTA_TOK_* kind of the tokens it consumes; RAW_TOKENS: that follows from PairPolicyDev::raw
+//   da / dt / np(raw)   features per agent row / per task row, and the env-uniform inputs in front of them in layer 1's chain
+//   LIST_IN_BLOCK       the list of valid cells sits in the scratch block (LIST) instead of the idle LDS in front of Scratch::resid
+//   SIGMOID             score = sigmoid of the logit clipped to +-20 (and pad pairs are masked) instead of tanhf(logit) * clamp
+//   GATE, FLAGS, FILL   its plan's MUAVTA_GATE_* and MUAVTA_SC_* flags, and whether that plan reads masked cells (they are written as 0)
+//   MAX_WAVES           waves per SIMD its rollout instantiation is built for: the hidden activations live in registers
+// MLP-Pair (muavta_set_pair_policy): Linear(25|20, 128) - ReLU - Linear(128, 128) - ReLU - Linear(128, 1) over build_pair_tokens(env, 32, 16).
+struct PolPair {
+  typedef PackedMlp<128, 25> W;
+  typedef TokenBlock<32, 13, 12> Blk;
+  enum { KIND = POL_PAIR, FLOATS = (Blk::END + 3) & ~3, RAW_TOKENS = 1, LIST_IN_BLOCK = 0, SIGMOID = 0,
+         GATE = MUAVTA_GATE_TRAINER, FLAGS = MUAVTA_SC_EDGE_VALID_ONLY, FILL = 0, MAX_WAVES = 3 };
+  static constexpr int tok_kind(int raw) { return raw ? MUAVTA_TOK_PAIR_RAW : MUAVTA_TOK_PAIR; }
+  static constexpr int da(bool raw) { return raw ? 11 : 12; }
+  static constexpr int dt(bool raw) { return raw ? 9 : 13; }
+  static constexpr int np(bool) { return 0; }
+};
+// MLP-ContextPair (muavta_set_context_pair_policy): MLPContextPairNet.pair_mlp, Linear(58|41, 192) - ReLU - Linear(192, 192) - ReLU - Linear(192, 1).
+// MLP-Pair's tokens, gate and plan; layer 1's columns permuted to a_pool, t_pool, context, agent, task; and a larger scratch block: the MLP-Pair
+// block, then the env-uniform head of layer 1's input row — a_pool [12|11], t_pool [13|9], context [8|1], contiguous (PRE; sim/policy.inc:
+// context_prefix) — and the 192 chains' values after those inputs (HEAD: computed once per plan, every pair's chain continues from them).
+struct PolContextPair : PolPair {
+  typedef PackedMlp<192, 58> W;
+  enum { KIND = POL_CONTEXT_PAIR, PRE = PolPair::FLOATS, HEAD = PRE + 36, FLOATS = HEAD + W::HID, MAX_WAVES = 2 };
+  static constexpr int np(bool raw) { return da(raw) + dt(raw) + (raw ? 1 : 8); }
+};
 // MLP-Coalition (muavta_set_pair_policy with raw_features == MUAVTA_TOK_ESCORT): MLPCoalitionNet.pair_mlp, Linear(38, 256) - ReLU - Linear(256, 256) -
-// ReLU - Linear(256, 1) over the escort tokens (agent 16 + task 22 features, 16 x 48 pairs), packed in the same order.  Its per-env scratch
-// block (PE_*, the weights are PWE_*; a buffer of its own, allocated when a policy of this kind is first installed): build_escort_tokens(env, 48, 16) of the plan
-// being made, its scores, and the list of valid cells (768 x u16 — more than the idle LDS in front of Scratch::resid holds on every tile).
-enum { PWE_HID = 256, PWE_W0_ROWS = 38,
-       PWE_W0 = 0, PWE_B0 = PWE_W0 + PWE_HID * PWE_W0_ROWS, PWE_W1 = PWE_B0 + PWE_HID, PWE_B1 = PWE_W1 + PWE_HID * PWE_HID, PWE_W2 = PWE_B1 + PWE_HID,
-       PWE_B2 = PWE_W2 + PWE_HID, PWE_FLOATS = PWE_B2 + 16 };
-enum { PE_MA = 16, PE_MT = 48,
-       PE_TF = 0, PE_AF = PE_TF + PE_MT * 22, PE_EV = PE_AF + PE_MA * 16, PE_SCORES = PE_EV + PE_MA * PE_MT, PE_TID = PE_SCORES + PE_MA * PE_MT,
-       PE_AID = PE_TID + PE_MT, PE_TMASK = PE_AID + PE_MA, PE_AMASK = PE_TMASK + PE_MT / 4, PE_LIST = PE_AMASK + PE_MA / 4,
-       PE_FLOATS = (PE_LIST + PE_MA * PE_MT / 2 + 3) & ~3 };
-// ESC: escort tokens, a 16 x 48 grid, the sigmoid score and the valid-cell list in the env's scratch block
-struct PairLayout { enum { CTX = 0, ESC = 0, HID = PW_HID, W0_ROWS = PW_W0_ROWS, W0 = PW_W0, B0 = PW_B0, W1 = PW_W1, B1 = PW_B1, W2 = PW_W2, B2 = PW_B2 }; };
-struct ContextPairLayout { enum { CTX = 1, ESC = 0, HID = PC_HID, W0_ROWS = PC_W0_ROWS, W0 = PC_W0, B0 = PC_B0, W1 = PC_W1, B1 = PC_B1, W2 = PC_W2, B2 = PC_B2 }; };
-struct CoalitionLayout { enum { CTX = 0, ESC = 1, HID = PWE_HID, W0_ROWS = PWE_W0_ROWS, W0 = PWE_W0, B0 = PWE_B0, W1 = PWE_W1, B1 = PWE_B1, W2 = PWE_W2, B2 = PWE_B2 }; };
+// ReLU - Linear(256, 1) over build_escort_tokens(env, 48, 16) (agent 16 + task 22 features, 16 x 48 pairs).  Its scratch block (a buffer of its
+// own, allocated when a policy of this kind is first installed) ends with the list of valid cells: 768 x u16 — more than the idle LDS in front
+// of Scratch::resid holds on every tile.
+struct PolCoalition {
+  typedef PackedMlp<256, 38> W;
+  typedef TokenBlock<48, 22, 16> Blk;
+  enum { KIND = POL_COALITION, LIST = Blk::END, FLOATS = (LIST + Blk::MA * Blk::MT / 2 + 3) & ~3, RAW_TOKENS = 0, LIST_IN_BLOCK = 1, SIGMOID = 1,
+         GATE = MUAVTA_GATE_ESCORT, FLAGS = MUAVTA_SC_COMMIT, FILL = 1, MAX_WAVES = 1 };
+  static constexpr int tok_kind(int) { return MUAVTA_TOK_ESCORT; }
+  static constexpr int da(bool) { return 16; }
+  static constexpr int dt(bool) { return 22; }
+  static constexpr int np(bool) { return 0; }
+};
+// (the values of the PW_* / PC_* / PWE_* and PS_* / PSC_* / PE_* enums these templates replace: neither layout may move)
+static_assert(PolPair::W::FLOATS == 19984 && PolContextPair::W::FLOATS == 48592 && PolCoalition::W::FLOATS == 76048, "packed-weight layout");
+static_assert(PolPair::FLOATS == 1692 && PolPair::Blk::SCORES == 1120 && PolContextPair::PRE == 1692 && PolContextPair::HEAD == 1728 &&
+              PolContextPair::FLOATS == 1920, "MLP-Pair / MLP-ContextPair scratch block");
+static_assert(PolCoalition::Blk::SCORES == 2080 && PolCoalition::LIST == 2928 && PolCoalition::FLOATS == 3312, "MLP-Coalition scratch block");
 
 template <class TL>
 struct Sim {

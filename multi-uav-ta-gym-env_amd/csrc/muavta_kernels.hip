@@ -289,11 +289,27 @@ __global__ __launch_bounds__(WG, TILE_MIN_WAVES(TL)) void k_step(const DevCtx* _
 }
 
 enum { SCORED_EXTRA_LDS = 128 };  // allocate<true>'s task list: one byte per slot, behind the tile
-// BL: the classical baselines (MUAVTA_ALLOC_CAP_GREEDY, MUAVTA_ALLOC_PI; sim/baselines.inc) in instantiations of their own
-// PM: the learned MLP-Pair hybrid (MUAVTA_ALLOC_MLP_PAIR; sim/policy.inc), likewise; launched with SCORED_EXTRA_LDS bytes behind the tile
-// CX (with PM): the installed policy is an MLP-ContextPair (192 wide, pooled rows and the context summary in front of every pair's inputs)
-// CO (with PM): the installed policy is an MLP-Coalition (256 wide over the escort tokens, a 16 x 48 grid, sigmoid scores, commit locks)
-template <class TL, bool BL = false, bool PM = false, bool CX = false, bool CO = false>
+// The allocator a k_allocate / k_rollout instantiation runs, as ONE tag type: the Hungarian family and the classical baselines pick their
+// variant from the run-time `mode`; a learned policy is named by its traits (muavta_device.h).  A tag gives the LDS its kernels need behind
+// the tile (allocate<true>'s task list) and the waves per SIMD its rollout is built for.  A fourth learned policy is a traits type next to
+// the three in muavta_device.h, whatever of sim/policy.inc's forward pass its traits cannot express, and one line each in with_policy
+// and for_each_policy (abi/handle.inc): every kernel instantiation, launch attribute and host-side size follows from there.
+struct AllocHungarian { enum { EXTRA_LDS = 0, MAX_WAVES = 8 }; };  // MUAVTA_ALLOC_HUNGARIAN .. _HUNGARIAN_GATED (sim/allocate.inc)
+struct AllocBaseline { enum { EXTRA_LDS = 0, MAX_WAVES = 8 }; };   // MUAVTA_ALLOC_CAP_GREEDY, _PI (sim/baselines.inc): the Hungarian kernels do not carry this code
+template <class POL>
+struct AllocLearned { typedef POL Pol; enum { EXTRA_LDS = SCORED_EXTRA_LDS, MAX_WAVES = POL::MAX_WAVES }; };  // MUAVTA_ALLOC_MLP_PAIR (sim/policy.inc)
+// The one place that turns a tag into the allocator's call.  sc_list: EXTRA_LDS bytes of LDS behind the tile.  A macro on purpose: as a
+// function (free or a member of Sim, both tried) the helper is one more level for the inliner, and with it the instruction streams of 24 of
+// the code object's 83 functions change (every k_rollout but the baselines', every learned k_allocate; two swapped instructions in the
+// Hungarian rollouts, 10 more VGPRs in k_allocate<.., AllocLearned<PolCoalition>>): profiles/allocator_tags_kernel_identity.txt.
+#define RUN_ALLOCATOR(AL, sim, ctx, env, interval, use_vis, mode, sc_list)                                                                  \
+  {                                                                                                                                        \
+    if constexpr (std::is_same<AL, AllocHungarian>::value) (sim).allocate(interval, use_vis, mode);                                        \
+    else if constexpr (std::is_same<AL, AllocBaseline>::value) (sim).allocate_baseline(interval, use_vis, mode);                           \
+    else (sim).template allocate_learned<typename AL::Pol>(interval, use_vis, (ctx).pol, as_global((ctx).pol.scratch) + (size_t)(env) * AL::Pol::FLOATS, sc_list); \
+  }
+
+template <class TL, class AL>
 __global__ __launch_bounds__(WG) void k_allocate(const DevCtx* __restrict__ ctxp, int interval, int use_vis, int mode,
                                                  int32_t* out_agent, int32_t* out_index, int act_cap, int env_base) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -303,11 +319,7 @@ __global__ __launch_bounds__(WG) void k_allocate(const DevCtx* __restrict__ ctxp
   copy16(L.S, blob, sizeof(EnvState<TL>));
   lds_sync();
   Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, tape_of(ctx, env));
-  if constexpr (PM && CO) sim.allocate_coalition(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PE_FLOATS, smem + Lds<TL>::bytes());
-  else if constexpr (PM && CX) sim.template allocate_mlp<true>(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PSC_FLOATS, smem + Lds<TL>::bytes());
-  else if constexpr (PM) sim.allocate_mlp(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PS_FLOATS, smem + Lds<TL>::bytes());
-  else if constexpr (BL) sim.allocate_baseline(interval, use_vis, mode);
-  else sim.allocate(interval, use_vis, mode);
+  RUN_ALLOCATOR(AL, sim, ctx, env, interval, use_vis, mode, smem + Lds<TL>::bytes());
   lds_sync();
   if (out_agent) {
     const EnvState<TL>& S = *L.S;
@@ -532,7 +544,7 @@ struct RecordPtrs {
 struct RecBlob { uint32_t w[64]; };  // 256 B: a RecordPtrs<TL> by value
 __global__ void k_store_rec(RecBlob b, uint32_t* dst) { dst[threadIdx.x] = b.w[threadIdx.x]; }
 
-template <class TL, bool REC, bool BL = false, bool PM = false, bool CX = false, bool CO = false>
+template <class TL, bool REC, class AL>
 __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned char* lds_own, uint32_t lds_base, int env, int phases, int interval, int use_vis, int mode,
                                                 const RecordPtrs<TL>& rec, int slot, int oslot) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -559,14 +571,7 @@ __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned cha
   }
   lds_sync();
   if (!ABL(9) && (phases & PH_ALLOC) && !(L.S->terminated || L.S->truncated)) {
-    if constexpr (PM && CO) sim.allocate_coalition(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PE_FLOATS,
-                                                   reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS);
-    else if constexpr (PM && CX) sim.template allocate_mlp<true>(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PSC_FLOATS,
-                                                            reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS);
-    else if constexpr (PM) sim.allocate_mlp(interval, use_vis, ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * PS_FLOATS,
-                                       reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS);
-    else if constexpr (BL) sim.allocate_baseline(interval, use_vis, mode);
-    else sim.allocate(interval, use_vis, mode);
+    RUN_ALLOCATOR(AL, sim, ctx, env, interval, use_vis, mode, reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS);
     if (REC && rec.K.task_feats) {  // the sample of step `slot`: tokens + labels of the plan just staged, S_WPS before the step
       const typename Sim<TL>::TokPtrs K = global_tok_ptrs<TL>(rec.K);
       cold_sync();
@@ -578,11 +583,11 @@ __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned cha
   PROF_AT(sim, 20);
 }
 
-// (PM: the forward pass keeps a pair's 128 hidden activations in registers, ~145 VGPRs — those instantiations are built for three waves
-// per SIMD, 168 VGPRs, where the tile's other kernels are built for four; CX: 192 activations, two waves per SIMD, 256 VGPRs;
-// CO: 256 activations, one wave per SIMD — about 480 of the unified 512-entry register file, the allocator's placement, no spill)
-template <class TL, bool REC, bool BL = false, bool PM = false, bool CX = false, bool CO = false>
-__global__ __launch_bounds__(WG, PM ? (CO ? 1 : TILE_MIN_WAVES(TL) < (CX ? 2 : 3) ? TILE_MIN_WAVES(TL) : (CX ? 2 : 3)) : TILE_MIN_WAVES(TL)) void k_rollout(const DevCtx* __restrict__ ctxp, const uint64_t* seeds, int n_steps, int interval, int use_vis,
+// (a learned policy's forward pass keeps a pair's hidden activations in registers, so AL caps the waves per SIMD its instantiations are
+// built for — PolPair: 128 activations, ~145 VGPRs, three waves, 168 VGPRs, where the tile's other kernels are built for four; PolContextPair:
+// 192, two waves, 256 VGPRs; PolCoalition: 256, one wave — about 480 of the unified 512-entry register file, the allocator's placement, no spill)
+template <class TL, bool REC, class AL>
+__global__ __launch_bounds__(WG, TILE_MIN_WAVES(TL) < AL::MAX_WAVES ? TILE_MIN_WAVES(TL) : AL::MAX_WAVES) void k_rollout(const DevCtx* __restrict__ ctxp, const uint64_t* seeds, int n_steps, int interval, int use_vis,
                                                 int mode, int write_obs, double* metrics, const uint32_t* seedbuf, const RecordPtrs<TL>* __restrict__ recp, int epoch, int env_base) {
   const DevCtx& ctx = ctx_ref(ctxp);
   // The ring pointers of muavta_rollout_record sit in device memory (one slot per handle, written on the launch's stream just ahead of
@@ -593,7 +598,7 @@ __global__ __launch_bounds__(WG, PM ? (CO ? 1 : TILE_MIN_WAVES(TL) < (CX ? 2 : 3
   // (unsigned halves: v_readfirstlane returns int, and a low word with bit 31 set would sign-extend into the high word)
   const RecordPtrs<TL>& rec = *(const RecordPtrs<TL>*)(const AS4 RecordPtrs<TL>*)(((uint64_t)rec_hi << 32) | (uint64_t)rec_lo);
   const int env = env_base + blockIdx.x;
-  __shared__ __align__(16) unsigned char lds_own[Lds<TL>::bytes() + PROF_EXTRA_LDS + (PM ? SCORED_EXTRA_LDS : 0)];  // KERNEL_LDS(TL) (+ PM: allocate<true>'s task list)
+  __shared__ __align__(16) unsigned char lds_own[Lds<TL>::bytes() + PROF_EXTRA_LDS + AL::EXTRA_LDS];  // KERNEL_LDS(TL) (+ a learned policy: allocate<true>'s task list)
   Lds<TL> L(lds_own);
   EnvState<TL>* blob = blob_of<TL>(ctx, env);
   Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, tape_of(ctx, env));
@@ -675,7 +680,7 @@ static_assert(MUAVTA_PACE_HOLD_POLLS > 0 && MUAVTA_PACE_HOLD_POLLS <= (1 << 16),
       if (threadIdx.x < 16) seen = __hip_atomic_load(pace_row + threadIdx.x, __ATOMIC_RELAXED, MUAVTA_PACE_SCOPE);
     }
 #endif
-    if (ph) rollout_phase<TL, REC, BL, PM, CX, CO>(ctxp, lds_own, lds_base, env, ph, interval, use_vis, mode, rec, k < n_steps ? k : n_steps,
+    if (ph) rollout_phase<TL, REC, AL>(ctxp, lds_own, lds_base, env, ph, interval, use_vis, mode, rec, k < n_steps ? k : n_steps,
                                    (REC && rec.O.tasks && k >= 1 && k <= n_steps) ? k - 1 : -1);
 #if MUAVTA_PACE_PRIO
     if (PACED && k >= 1 && k <= n_steps && (k & (MUAVTA_PACE_EVERY - 1)) == 0) {  // consumed a step later: the load's latency stays off the env's dependent chain
@@ -771,11 +776,10 @@ __global__ __launch_bounds__(WG) void k_tokens(const DevCtx* __restrict__ ctxp, 
   sim.tokens(K, env);
 }
 
-// muavta_pair_scores(_device): the MLP-Pair policy's scores / logits of every env's CURRENT state — build_pair_tokens(env, 32, 16) into
-// the env's scratch block, then the forward pass of sim/policy.inc, the same code the MUAVTA_ALLOC_MLP_PAIR mode runs at a replan.
-// scores / logits: [N, 16, 32] (either may be null); entries whose edge_valid is 0 are written as 0.  The env records are not changed.
-// CX: the installed policy is an MLP-ContextPair.  CO: an MLP-Coalition — build_escort_tokens(env, 48, 16), scores / logits [N, 16, 48].
-template <class TL, bool CX = false, bool CO = false>
+// muavta_pair_scores(_device): the installed policy's scores / logits of every env's CURRENT state — POL's tokens into the env's scratch
+// block, then the forward pass of sim/policy.inc, the same code the MUAVTA_ALLOC_MLP_PAIR mode runs at a replan.  scores / logits:
+// [N, 16, POL::Blk::MT] (either may be null); entries whose edge_valid is 0 are written as 0.  The env records are not changed.
+template <class TL, class POL>
 __global__ __launch_bounds__(WG) void k_pair_scores(const DevCtx* __restrict__ ctxp, float* scores, float* logits) {
   const DevCtx& ctx = ctx_ref(ctxp);
   const int env = blockIdx.x;
@@ -783,21 +787,11 @@ __global__ __launch_bounds__(WG) void k_pair_scores(const DevCtx* __restrict__ c
   copy16(L.S, blob_of<TL>(ctx, env), sizeof(EnvState<TL>));
   lds_sync();
   Sim<TL> sim(*L.S, *cold_of<TL>(ctx, env), *L.X, ctx.P, nullptr);
-  float* scratch = as_global(ctx.pol.scratch) + (size_t)env * (CO ? PE_FLOATS : CX ? PSC_FLOATS : PS_FLOATS);
-  if constexpr (CO) {
-    const size_t at = (size_t)env * PE_MA * PE_MT;
-    sim.coalition_tokens_scratch(scratch);
-    sim.coalition_forward(ctx.pol, scratch, scores ? as_global(scores) + at : nullptr, logits ? as_global(logits) + at : nullptr);
-    return;
-  }
-  sim.pair_tokens_scratch(ctx.pol, scratch);
-  const size_t at = (size_t)env * PS_MA * PS_MT;
-  if constexpr (CX) {
-    sim.context_prefix(ctx.pol, scratch);
-    sim.context_pair_forward(ctx.pol, scratch, scores ? as_global(scores) + at : nullptr, logits ? as_global(logits) + at : nullptr, true);
-  } else
-  sim.pair_forward(ctx.pol, scratch + PS_TF, scratch + PS_AF, scratch + PS_EV, scores ? as_global(scores) + at : nullptr,
-                   logits ? as_global(logits) + at : nullptr, true);
+  float* scratch = as_global(ctx.pol.scratch) + (size_t)env * POL::FLOATS;
+  sim.template policy_tokens<POL>(ctx.pol, scratch);
+  const size_t at = (size_t)env * POL::Blk::MA * POL::Blk::MT;
+  if constexpr (POL::np(false) > 0) sim.context_prefix(ctx.pol, scratch);
+  sim.template policy_forward<POL>(ctx.pol, scratch, scores ? as_global(scores) + at : nullptr, logits ? as_global(logits) + at : nullptr, true);
 }
 
 template <class TL>

@@ -1,6 +1,6 @@
 // sim/baselines.inc — member functions of Sim<TL> (muavta_device.h includes this file INSIDE the struct body): the two classical
 // baselines of the reference's tables, MUAVTA_ALLOC_CAP_GREEDY and MUAVTA_ALLOC_PI (include/muavta.h).  Compiled only into the
-// baseline instantiations of k_rollout / k_allocate (BL = true): the Hungarian kernels do not carry this code.
+// baseline instantiations of k_rollout / k_allocate (AllocBaseline): the Hungarian kernels do not carry this code.
 // Result: S.act_agent / S.act_slot / S.act_index, S.n_act, with the _apply_assign filter of the Hungarian path (a task that is
 // not in env.last_tasks_info is dropped; experiments/wps_eval.py:55-61).
   // str(x) < str(y) for x, y >= 0: digit strings compare as the numbers padded to the same length, a prefix sorts first

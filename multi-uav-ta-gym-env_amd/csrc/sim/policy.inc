@@ -19,33 +19,36 @@
   typedef float pol_f2 __attribute__((ext_vector_type(2)));
   static DEV float pol_relu(float v) { return v > 0.f ? v : 0.f; }
   static DEV const float* as_global_f(const float* p) { return (const float*)(const __attribute__((address_space(1))) float*)p; }
-  // tf / af / ev: this env's token tensors ([32, Dt], [16, Da], [16, 32]) in global memory, complete and visible (cold_sync() by the
-  // caller).  scores / logits: this env's [16, 32] outputs (either may be null).  fill: masked entries are written as 0 (the fused mode
+  // blk: this env's scratch block (POL::FLOATS), its token tensors ([MT, Dt], [16, Da], [16, MT]) complete and visible (cold_sync() by the
+  // caller).  scores / logits: this env's [16, MT] outputs (either may be null).  fill: masked entries are written as 0 (MLP-Pair's fused mode
   // leaves them alone: allocate<true> under MUAVTA_SC_EDGE_VALID_ONLY never reads them).  Scratch: X.cost .. X.spc (the list of valid cells).
-  // LY: PairLayout (MLP-Pair, 128 wide) or ContextPairLayout (MLP-ContextPair, 192 wide; `pre`: the env-uniform head of layer 1's input row
-  // in the env's scratch block, context_prefix() below, with the 192 floats of PSC_HEAD behind it) — the packed-weight offsets and the width, everything else is the same code.
-  // CoalitionLayout (MLP-Coalition, 256 wide, LY::ESC): escort token rows (agent 16 + task 22 features), a 16 x 48 grid, score = sigmoid of the
-  // logit clipped to +-20, and `glist`: the list of valid cells in the env's scratch block (PE_LIST) — 1,536 B do not fit in front of Scratch::resid.
-  // tpad / apad (LY::ESC): the token builder's task_mask / agent_mask (1 = pad row); a pair of a pad row is masked like one whose edge_valid is 0.
-  template <bool RAW, class LY>
-  DEV void pair_forward_t(const PairPolicyDev& pol, const float* tf, const float* af, const float* ev, float* scores, float* logits, bool fill, const float* pre,
-                          uint16_t* glist = nullptr, const uint8_t* tpad = nullptr, const uint8_t* apad = nullptr) {
-    constexpr int Da = LY::ESC ? 16 : RAW ? 11 : 12, Dt = LY::ESC ? 22 : RAW ? 9 : 13, NP = LY::CTX ? Da + Dt + (RAW ? 1 : 8) : 0, K0 = NP + Da + Dt, HID = LY::HID;
-    constexpr int MT = LY::ESC ? (int)PE_MT : (int)PS_MT, CELLS = PS_MA * MT;
-    static_assert(K0 <= LY::W0_ROWS && HID % 64 == 0 && PE_MA == PS_MA, "layer 1's weights are stored k-major, W0_ROWS rows of HID");
+  // POL: the policy's traits (muavta_device.h) — the packed-weight offsets and the width, the feature widths and the grid, the env-uniform head of
+  // layer 1's input row (PolContextPair: `pre`, written by context_prefix() below, with the 192 floats of HEAD behind it), the score function and
+  // the place of the list of valid cells (PolCoalition: 1,536 B do not fit in front of Scratch::resid) — everything else is the same code.
+  // tpad / apad (POL::SIGMOID): the token builder's task_mask / agent_mask (1 = pad row); a pair of a pad row is masked like one whose edge_valid is 0.
+  template <bool RAW, class POL>
+  DEV void pair_forward_t(const PairPolicyDev& pol, float* blk, float* scores, float* logits, bool fill) {
+    typedef typename POL::W LY;
+    typedef typename POL::Blk B;
+    constexpr int Da = POL::da(RAW), Dt = POL::dt(RAW), NP = POL::np(RAW), K0 = NP + Da + Dt, HID = LY::HID;
+    constexpr int MT = B::MT, CELLS = B::MA * MT;
+    static_assert(K0 <= LY::W0_ROWS && HID % 64 == 0, "layer 1's weights are stored k-major, W0_ROWS rows of HID");
     // the list of valid cells: the cost tile and the LSAP's duals / spc behind it (one run of doubles, all idle between the token builder and the plan)
-    static_assert(LY::ESC || (offsetof(Scratch<TL>, resid) - offsetof(Scratch<TL>, cost) >= CELLS * sizeof(uint16_t) && offsetof(Scratch<TL>, u) > offsetof(Scratch<TL>, cost) &&
+    static_assert(POL::LIST_IN_BLOCK || (offsetof(Scratch<TL>, resid) - offsetof(Scratch<TL>, cost) >= CELLS * sizeof(uint16_t) && offsetof(Scratch<TL>, u) > offsetof(Scratch<TL>, cost) &&
                   offsetof(Scratch<TL>, resid) > offsetof(Scratch<TL>, spc)), "the list of valid cells needs 1 KB in front of Scratch::resid");
+    const float *tf = blk + B::TF, *af = blk + B::AF, *ev = blk + B::EV, *pre = nullptr;
+    if constexpr (NP > 0) pre = blk + POL::PRE;
+    const uint8_t *tpad = reinterpret_cast<const uint8_t*>(blk + B::TMASK), *apad = reinterpret_cast<const uint8_t*>(blk + B::AMASK);
     const uint64_t wb = (uint64_t)pol.w;
     uint32_t wlo = __builtin_amdgcn_readfirstlane((uint32_t)wb), whi = __builtin_amdgcn_readfirstlane((uint32_t)(wb >> 32));
     const float clamp = pol.clamp;
     uint16_t* list;
-    if constexpr (LY::ESC) list = glist; else list = reinterpret_cast<uint16_t*>(X.cost);
+    if constexpr (POL::LIST_IN_BLOCK) list = reinterpret_cast<uint16_t*>(blk + POL::LIST); else list = reinterpret_cast<uint16_t*>(X.cost);
     int nv = 0;
     for (int base = 0; base < CELLS; base += WG) {
       const int c = base + lane;
       bool v = ev[c] != 0.f;
-      if constexpr (LY::ESC) v = v && tpad[c % MT] == 0 && apad[c / MT] == 0;  // (pad pairs are masked here too, whatever edge_valid holds)
+      if constexpr (POL::SIGMOID) v = v && tpad[c % MT] == 0 && apad[c / MT] == 0;  // (pad pairs are masked here too, whatever edge_valid holds)
       const unsigned long long m = __ballot(v);
       if (v) list[nv + prefix_count(m)] = (uint16_t)c;
       else if (fill) {
@@ -54,12 +57,13 @@
       }
       nv += __popcll(m);
     }
-    // CTX: the first NP inputs of layer 1 (a_pool, t_pool, context) are the same for every pair of the env, so the chains' values after them
+    // NP > 0: the first NP inputs of layer 1 (a_pool, t_pool, context) are the same for every pair of the env, so the chains' values after them
     // are computed ONCE per plan — output n on lane n % 64, the same fmaf steps in the same order, hence the same bits — and parked in the
-    // env's scratch block (PSC_HEAD); every pair's chain continues from there.  Written and read back with vector accesses: not through
+    // env's scratch block (POL::HEAD); every pair's chain continues from there.  Written and read back with vector accesses: not through
     // the scalar cache, which may still hold the line of the previous plan.
-    float* head = LY::CTX ? const_cast<float*>(pre) + (PSC_HEAD - PSC_PRE) : nullptr;
-    if constexpr (LY::CTX) {
+    float* head = nullptr;
+    if constexpr (NP > 0) {
+      head = blk + POL::HEAD;
       if (nv > 0) {  // (uniform)
         const float* wg = as_global_f(pol.w);
         for (int n = lane; n < HID; n += WG) {
@@ -71,7 +75,7 @@
       }
       cold_sync();  // every lane's outputs are in memory before any lane reads another's
     }
-    if constexpr (LY::ESC) cold_sync();  // the list is in global memory: every lane's entries are there before any lane reads another's
+    if constexpr (POL::LIST_IN_BLOCK) cold_sync();  // the list is in global memory: every lane's entries are there before any lane reads another's
     lds_sync();
     for (int b0 = 0; b0 < nv; b0 += WG) {  // (uniform)
       // (the weights' base is made opaque once per pass: otherwise layer 1's 128 biases — pass-invariant scalar loads — are hoisted in
@@ -93,7 +97,7 @@
       for (int nc = 0; nc < HID / 2; nc += 32) {
 #pragma unroll
         for (int t = 0; t < 32; t++) {
-          if constexpr (LY::CTX) h1[nc + t] = pol_f2{head[2 * (nc + t)], head[2 * (nc + t) + 1]};
+          if constexpr (NP > 0) h1[nc + t] = pol_f2{head[2 * (nc + t)], head[2 * (nc + t) + 1]};
           else h1[nc + t] = pol_f2{w[LY::B0 + 2 * (nc + t)], w[LY::B0 + 2 * (nc + t) + 1]};
         }
 #pragma unroll 1
@@ -172,16 +176,12 @@
       }
       if (act) {
         if (logits) logits[c] = logit;
-        if constexpr (LY::ESC) {  // AttentionEscort.act: 1 / (1 + exp(-clip(logit, -20, 20))), float32, IEEE division
+        if constexpr (POL::SIGMOID) {  // AttentionEscort.act: 1 / (1 + exp(-clip(logit, -20, 20))), float32, IEEE division
           if (scores) scores[c] = 1.0f / (1.0f + expf(-fminf(fmaxf(logit, -20.0f), 20.0f)));
         } else if (scores) scores[c] = tanhf(logit) * clamp;
       }
     }
     lds_sync();
-  }
-  DEV void pair_forward(const PairPolicyDev& pol, const float* tf, const float* af, const float* ev, float* scores, float* logits, bool fill) {
-    if (pol.raw) pair_forward_t<true, PairLayout>(pol, tf, af, ev, scores, logits, fill, nullptr);  // (uniform)
-    else pair_forward_t<false, PairLayout>(pol, tf, af, ev, scores, logits, fill, nullptr);
   }
   // ---- MLP-ContextPair: ContextPairHybrid(use_attention=False) (TaskAllocation/Hybrid/ContextPairHybrid.py:154-210) --------------------
   //   pair = cat([agent_feats[i], task_feats[j], a_pool, t_pool, context]);  logits = pair_mlp(pair)   Linear(58|41, 192) - ReLU - Linear(192, 192) - ReLU - Linear(192, 1)
@@ -191,34 +191,31 @@
   //   * layer 1: one fmaf chain per output from the bias over a_pool, t_pool, context, the agent row, the task row (each ascending) — the
   //     env-uniform inputs first, the state_dict's columns (agent, task, a_pool, t_pool, context) are permuted when the weights are packed;
   //   * ReLU, layers 2 and 3, tanhf, the masked pairs: as above.
-  // context_prefix: the 25 + 8 (raw: 20 + 1) env-uniform inputs into the env's scratch block behind the MLP-Pair layout (PSC_PRE).  One
+  // context_prefix: the 25 + 8 (raw: 20 + 1) env-uniform inputs into the env's scratch block behind the MLP-Pair layout (PolContextPair::PRE).  One
   // column per lane; the forward pass reads them back with vector loads (every lane the same address) and runs the chains' env-uniform
   // head once per plan (pair_forward_t).
   template <bool RAW>
   DEV void context_prefix_t(float* base) {
-    constexpr int Da = RAW ? 11 : 12, Dt = RAW ? 9 : 13;
-    float* pre = base + PSC_PRE;
+    typedef PolContextPair::Blk B;
+    constexpr int Da = PolContextPair::da(RAW), Dt = PolContextPair::dt(RAW);
+    float* pre = base + PolContextPair::PRE;
     if (lane < Da + Dt) {
       const bool ag = lane < Da;
-      const int d = ag ? lane : lane - Da, rows = ag ? PS_MA : PS_MT, D = ag ? Da : Dt;
-      const float* x = base + (ag ? PS_AF : PS_TF);
-      const uint8_t* pad = reinterpret_cast<const uint8_t*>(base + (ag ? PS_AMASK : PS_TMASK));
+      const int d = ag ? lane : lane - Da, rows = ag ? B::MA : B::MT, D = ag ? Da : Dt;
+      const float* x = base + (ag ? B::AF : B::TF);
+      const uint8_t* pad = reinterpret_cast<const uint8_t*>(base + (ag ? B::AMASK : B::TMASK));
       float s = 0.0f;
       int count = 0;
       for (int r = 0; r < rows; r++)
         if (pad[r] == 0) { s = s + x[r * D + d]; count++; }
       pre[lane] = s / (float)(count > 1 ? count : 1);
     }
-    context(RAW ? 1 : 0, PS_MT, pre + Da + Dt);
+    context(RAW ? 1 : 0, B::MT, pre + Da + Dt);
     cold_sync();  // the columns are in memory before the forward pass reads them across lanes
   }
   DEV void context_prefix(const PairPolicyDev& pol, float* base) {
     if (pol.raw) context_prefix_t<true>(base);  // (uniform)
     else context_prefix_t<false>(base);
-  }
-  DEV void context_pair_forward(const PairPolicyDev& pol, const float* base, float* scores, float* logits, bool fill) {
-    if (pol.raw) pair_forward_t<true, ContextPairLayout>(pol, base + PS_TF, base + PS_AF, base + PS_EV, scores, logits, fill, base + PSC_PRE);  // (uniform)
-    else pair_forward_t<false, ContextPairLayout>(pol, base + PS_TF, base + PS_AF, base + PS_EV, scores, logits, fill, base + PSC_PRE);
   }
   // ---- MLP-Coalition: AttentionEscort(use_attention=False) (TaskAllocation/Hybrid/AttentionEscort.py:326-367,370-524) ---------------------------
   //   logits = pair_mlp(cat([agent_feats[i], task_feats[j]]))      Linear(38, 256) - ReLU - Linear(256, 256) - ReLU - Linear(256, 1)
@@ -226,44 +223,23 @@
   //   edge_scores = every non-pad pair) + apply_agent_commits.  CONTRACT (DESIGN.md §7.1; tests/coalition_mlp_py.py): layer 1 is one chain over the
   //   agent row's 16 features, then the task row's 22; layers 2 and 3 as above; score = 1.0f / (1.0f + expf(-fminf(fmaxf(logit, -20.0f), 20.0f)));
   //   pad pairs and pairs whose edge_valid is 0 are not evaluated and score 0; score_clamp is not used.
-  // build_escort_tokens(env, 48, 16) of the current state into this env's PE_FLOATS block
-  DEV void coalition_tokens_scratch(float* base) {
+  // The forward pass of the installed policy over the env's scratch block (a network with env-uniform inputs: after context_prefix())
+  template <class POL>
+  DEV void policy_forward(const PairPolicyDev& pol, float* base, float* scores, float* logits, bool fill) {
+    if constexpr (!POL::RAW_TOKENS) pair_forward_t<false, POL>(pol, base, scores, logits, fill);
+    else if (pol.raw) pair_forward_t<true, POL>(pol, base, scores, logits, fill);  // (uniform)
+    else pair_forward_t<false, POL>(pol, base, scores, logits, fill);
+  }
+  // POL's tokens — build_pair_tokens(env, 32, 16[, raw]) or build_escort_tokens(env, 48, 16) — of the current state into this env's scratch block
+  template <class POL>
+  DEV void policy_tokens(const PairPolicyDev& pol, float* base) {
+    typedef typename POL::Blk B;
     TokPtrs K;
-    K.task_feats = base + PE_TF; K.agent_feats = base + PE_AF; K.edge_valid = base + PE_EV;
-    K.task_ids = reinterpret_cast<int32_t*>(base + PE_TID); K.agent_ids = reinterpret_cast<int32_t*>(base + PE_AID);
-    K.task_mask = reinterpret_cast<uint8_t*>(base + PE_TMASK); K.agent_mask = reinterpret_cast<uint8_t*>(base + PE_AMASK);
+    K.task_feats = base + B::TF; K.agent_feats = base + B::AF; K.edge_valid = base + B::EV;
+    K.task_ids = reinterpret_cast<int32_t*>(base + B::TID); K.agent_ids = reinterpret_cast<int32_t*>(base + B::AID);
+    K.task_mask = reinterpret_cast<uint8_t*>(base + B::TMASK); K.agent_mask = reinterpret_cast<uint8_t*>(base + B::AMASK);
     K.n_urgent = nullptr; K.expert_mask = nullptr; K.replanned = nullptr;
-    K.kind = MUAVTA_TOK_ESCORT; K.max_tasks = PE_MT; K.max_agents = PE_MA;
-    cold_sync();  // the token rows read currentReqs / allocatedReqs
-    tokens(K, 0);
-    cold_sync();  // every lane's rows are in memory before any lane reads another's
-  }
-  // masked cells are always written as 0: the plan below reads every non-pad cell (no MUAVTA_SC_EDGE_VALID_ONLY), and the reference's score there is 0
-  DEV void coalition_forward(const PairPolicyDev& pol, float* base, float* scores, float* logits) {
-    pair_forward_t<false, CoalitionLayout>(pol, base + PE_TF, base + PE_AF, base + PE_EV, scores, logits, true, nullptr, reinterpret_cast<uint16_t*>(base + PE_LIST),
-                                           reinterpret_cast<const uint8_t*>(base + PE_TMASK), reinterpret_cast<const uint8_t*>(base + PE_AMASK));
-  }
-  // MUAVTA_ALLOC_MLP_PAIR with a POL_COALITION policy: run_escort_episode's MLP-Coalition branch (experiments/escort_eval.py:181-188) —
-  //     if _should_replan(env, events, interval):  result, *_ = mlp.plan(env, hung_force, events=events, explore=False, force=True)
-  DEV void allocate_coalition(int interval, int use_visibility, const PairPolicyDev& pol, float* scratch, uint8_t* sc_list) {
-    if (gate_fires(MUAVTA_GATE_ESCORT, interval)) {
-      coalition_tokens_scratch(scratch);
-      coalition_forward(pol, scratch, scratch + PE_SCORES, nullptr);
-      cold_sync();  // the scores are in memory before the cost evaluation reads them across lanes
-    }
-    ScoredDev sc;
-    sc.scores = scratch + PE_SCORES; sc.pri = nullptr; sc.reserved = nullptr; sc.selected = nullptr; sc.replanned = nullptr;
-    sc.kind = MUAVTA_TOK_ESCORT; sc.MT = PE_MT; sc.MA = PE_MA; sc.gate = MUAVTA_GATE_ESCORT; sc.flags = MUAVTA_SC_COMMIT;
-    allocate<true>(interval, use_visibility, 4, &sc, 0, sc_list);
-  }
-  // build_pair_tokens(env, 32, 16[, raw]) of the current state into this env's scratch block
-  DEV void pair_tokens_scratch(const PairPolicyDev& pol, float* base) {
-    TokPtrs K;
-    K.task_feats = base + PS_TF; K.agent_feats = base + PS_AF; K.edge_valid = base + PS_EV;
-    K.task_ids = reinterpret_cast<int32_t*>(base + PS_TID); K.agent_ids = reinterpret_cast<int32_t*>(base + PS_AID);
-    K.task_mask = reinterpret_cast<uint8_t*>(base + PS_TMASK); K.agent_mask = reinterpret_cast<uint8_t*>(base + PS_AMASK);
-    K.n_urgent = nullptr; K.expert_mask = nullptr; K.replanned = nullptr;
-    K.kind = pol.raw ? 1 : 0; K.max_tasks = PS_MT; K.max_agents = PS_MA;
+    K.kind = POL::tok_kind(pol.raw); K.max_tasks = B::MT; K.max_agents = B::MA;
     cold_sync();  // the token rows read currentReqs / allocatedReqs
     tokens(K, 0);
     cold_sync();  // every lane's rows are in memory before any lane reads another's
@@ -272,21 +248,22 @@
   // wps_eval.py:244-254,490-492; train_pair_cost.py:73-93 with its own interval) —
   //     if _should_replan(env, events, interval):  tok = build_tokens(env); scores = score_tokens(tok); result = plan(.., scores=scores)
   // — tokens and scores only where the gate fires (uniform), then the scored Hungarian with the gate, the token pads and the flags the
-  // reference's plan uses.  scratch: this env's PS_FLOATS block; sc_list: T bytes of LDS behind the tile (allocate<true>'s task list).
-  // CX: the installed policy is an MLP-ContextPair (scratch: this env's PSC_FLOATS block).
-  template <bool CX = false>
-  DEV void allocate_mlp(int interval, int use_visibility, const PairPolicyDev& pol, float* scratch, uint8_t* sc_list) {
-    if (gate_fires(MUAVTA_GATE_TRAINER, interval)) {
-      pair_tokens_scratch(pol, scratch);
-      if constexpr (CX) {
-        context_prefix(pol, scratch);
-        context_pair_forward(pol, scratch, scratch + PS_SCORES, nullptr, false);
-      } else pair_forward(pol, scratch + PS_TF, scratch + PS_AF, scratch + PS_EV, scratch + PS_SCORES, nullptr, false);
+  // reference's plan uses (POL::GATE, POL::FLAGS).  With a PolCoalition policy: run_escort_episode's MLP-Coalition branch (experiments/escort_eval.py:181-188) —
+  //     if _should_replan(env, events, interval):  result, *_ = mlp.plan(env, hung_force, events=events, explore=False, force=True)
+  // — whose plan reads every non-pad cell (no MUAVTA_SC_EDGE_VALID_ONLY), so masked cells are written as 0, the reference's score there (POL::FILL).
+  // scratch: this env's POL::FLOATS block; sc_list: T bytes of LDS behind the tile (allocate<true>'s task list).
+  template <class POL>
+  DEV void allocate_learned(int interval, int use_visibility, const PairPolicyDev& pol, float* scratch, uint8_t* sc_list) {
+    typedef typename POL::Blk B;
+    if (gate_fires(POL::GATE, interval)) {
+      policy_tokens<POL>(pol, scratch);
+      if constexpr (POL::np(false) > 0) context_prefix(pol, scratch);
+      policy_forward<POL>(pol, scratch, scratch + B::SCORES, nullptr, POL::FILL);
       cold_sync();  // the scores are in memory before the cost evaluation reads them across lanes
     }
     ScoredDev sc;
-    sc.scores = scratch + PS_SCORES; sc.pri = nullptr; sc.reserved = nullptr; sc.selected = nullptr; sc.replanned = nullptr;
-    sc.kind = pol.raw ? 1 : 0; sc.MT = PS_MT; sc.MA = PS_MA; sc.gate = MUAVTA_GATE_TRAINER; sc.flags = MUAVTA_SC_EDGE_VALID_ONLY;
+    sc.scores = scratch + B::SCORES; sc.pri = nullptr; sc.reserved = nullptr; sc.selected = nullptr; sc.replanned = nullptr;
+    sc.kind = POL::tok_kind(pol.raw); sc.MT = B::MT; sc.MA = B::MA; sc.gate = POL::GATE; sc.flags = POL::FLAGS;
     allocate<true>(interval, use_visibility, 4, &sc, 0, sc_list);
   }
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register / spill / scratch / LDS figures of every kernel in a built libmuavta.so, read from the code object's metadata
-(builder's tool; no recompile).  usage: kernel_meta.py [path/to/libmuavta.so] [substring ...]"""
+(builder's tool; no recompile).  usage: kernel_meta.py [path/to/libmuavta.so] [substring ...]
+       kernel_meta.py NEW.so --diff OLD.so    both tables row by row, then every function's instruction stream (see diff())"""
 import os
 import re
 import subprocess
@@ -10,30 +11,35 @@ import tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-# names of the bool template arguments behind the tile (k_rollout<TL, REC, BL, PM, CX, CO>, k_allocate<TL, BL, PM, CX, CO>, k_pair_scores<TL, CX, CO>;
-# BL = the baseline allocators, PM = the learned pair policy, CX = that policy is an MLP-ContextPair, CO = it is an MLP-Coalition)
-FLAGS = {"k_rollout": ("REC", "BL", "PM", "CX", "CO"), "k_allocate": ("BL", "PM", "CX", "CO"), "k_pair_scores": ("CX", "CO")}
+# The template arguments behind the tile — k_rollout<TL, REC, AL>, k_allocate<TL, AL>, k_pair_scores<TL, POL> — printed as the tags the
+# committed tables use: REC = the recording rollout, BL = AllocBaseline, PM = AllocLearned<POL>, and with it (or for k_pair_scores alone)
+# CX = PolContextPair, CO = PolCoalition.  AllocHungarian and PolPair print nothing.
+TAGS = (("REC", "Lb1E"), ("BL", "AllocBaseline"), ("PM", "AllocLearned"), ("CX", "PolContextPair"), ("CO", "PolCoalition"))
 
 
 def short(name):
-    m = re.search(r"(k_\w+?)I4TileILi(\d+)ELi(\d+)E(?:L[ib]\d+E)*E((?:Lb\dE)*)", name)
+    m = re.search(r"(k_\w+?)I4TileILi(\d+)ELi(\d+)E(?:L[ib]\d+E)*E(.*?)Ev", name)
     if m:
+        tags = "".join(f",{t}" for t, s in TAGS if s in m.group(4))
         bits = re.findall(r"Lb(\d)E", m.group(4))
-        tags = "".join(f",{t}" for t, b in zip(FLAGS.get(m.group(1), ("REC",)), bits) if b == "1")
+        if len(bits) > 1 and re.fullmatch(r"(Lb\dE)+E*", m.group(4)):  # a build from before the tag types: one bool each, in this order (--diff against such a build)
+            tags = "".join(f",{t}" for t, b in zip(("REC", "BL", "PM", "CX", "CO")[-len(bits):], bits) if b == "1")
         return f"{m.group(1)}<{m.group(2)}x{m.group(3)}{tags}>"
     m = re.search(r"N_1\d+(k_\w+?)E", name)
     return m.group(1) if m else name[:60]
 
 
-def main():
-    so = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".so") else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "multi-uav-ta-gym-env_amd", "libmuavta.so")
-    subs = [a for a in sys.argv[1:] if not a.endswith(".so")]
+def code_object(so, d):
+    fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "k.co")
+    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", so, fat])
+    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}", "--unbundle"])
+    return co
+
+
+def table(so, subs=()):
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "k.co")
-        subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", so, fat])
-        subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}", "--unbundle"])
-        notes = subprocess.check_output([f"{LLVM}/llvm-readelf", "--notes", co], text=True)
-    print(f"{'kernel':34s} {'VGPR':>5s} {'vspill':>6s} {'SGPR':>5s} {'sspill':>6s} {'scratch B':>9s} {'LDS B':>7s}")
+        notes = subprocess.check_output([f"{LLVM}/llvm-readelf", "--notes", code_object(so, d)], text=True)
+    rows = [f"{'kernel':34s} {'VGPR':>5s} {'vspill':>6s} {'SGPR':>5s} {'sspill':>6s} {'scratch B':>9s} {'LDS B':>7s}"]
     for blk in notes.split("  - .agpr_count:")[1:]:
         def f(key):
             m = re.search(rf"\.{key}:\s+(\S+)", blk)
@@ -41,7 +47,62 @@ def main():
         name = short(f("name"))
         if subs and not any(s in name for s in subs):
             continue
-        print(f"{name:34s} {f('vgpr_count'):>5s} {f('vgpr_spill_count'):>6s} {f('sgpr_count'):>5s} {f('sgpr_spill_count'):>6s} {f('private_segment_fixed_size'):>9s} {f('group_segment_fixed_size'):>7s}")
+        rows.append(f"{name:34s} {f('vgpr_count'):>5s} {f('vgpr_spill_count'):>6s} {f('sgpr_count'):>5s} {f('sgpr_spill_count'):>6s} {f('private_segment_fixed_size'):>9s} {f('group_segment_fixed_size'):>7s}")
+    return rows
+
+
+def streams(so):
+    """[(symbol, [instruction text])] of every function in the code object, in order.  Masked: the 32-bit literal of an s_add_u32 / s_addc_u32
+    within three instructions after an s_getpc_b64 (a pc-relative address: it moves with .rodata and with the functions in front)."""
+    with tempfile.TemporaryDirectory() as d:
+        dis = subprocess.check_output([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", code_object(so, d)], text=True)
+    funcs = []
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]* ?<(.+)>:$", line)
+        if m:
+            funcs.append((m.group(1), []))
+        elif funcs and line.startswith("\t"):
+            funcs[-1][1].append(re.sub(r"\s*//.*$", "", line).strip())
+    for _, body in funcs:
+        for i, ins in enumerate(body):
+            if ins.startswith("s_getpc_b64"):
+                for j in range(i + 1, min(i + 4, len(body))):
+                    if re.match(r"s_addc?_u32 ", body[j]):
+                        body[j] = body[j].rsplit(",", 1)[0] + ", <pcrel>"
+    return funcs
+
+
+def diff(new, old):
+    """Same machine code?  (a) the two tables agree row for row; (b) every function's instruction stream is identical — per function, in
+    order, symbol names ignored, nothing masked but the pc-relative literals (streams()).  Exit status 1 if either differs."""
+    ta, tb = table(new), table(old)
+    print(f"new: {new}\nold: {old}\n\n(a) kernel table: {len(ta) - 1} kernels new, {len(tb) - 1} old")
+    bad = len(ta) != len(tb)
+    for a, b in zip(ta, tb):
+        same = a == b
+        bad |= not same
+        print(a if same else f"{a}   <-- old: {b}")
+    fa, fb = streams(new), streams(old)
+    n_ins = sum(len(body) for _, body in fa)
+    print(f"\n(b) instruction streams: {len(fa)} functions new, {len(fb)} old; {n_ins} instructions new")
+    differ = 0
+    for (na, ia), (nb, ib) in zip(fa, fb):
+        if ia != ib:
+            differ += 1
+            first = next((k for k, (x, y) in enumerate(zip(ia, ib)) if x != y), min(len(ia), len(ib)))
+            print(f"DIFFERENT {short(na)} / {short(nb)}: {len(ia)} against {len(ib)} instructions, {sum(x != y for x, y in zip(ia, ib))} differ in place, first at {first}")
+    bad |= differ != 0 or len(fa) != len(fb)
+    print(f"{len(fa) - differ} of {len(fa)} functions identical instruction for instruction" + ("" if differ else " (all)"))
+    return 1 if bad else 0
+
+
+def main():
+    args = sys.argv[1:]
+    if "--diff" in args:
+        i = args.index("--diff")
+        sys.exit(diff(args[0], args[i + 1]))
+    so = args[0] if args and args[0].endswith(".so") else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "multi-uav-ta-gym-env_amd", "libmuavta.so")
+    print("\n".join(table(so, [a for a in args if not a.endswith(".so")])))
 
 
 if __name__ == "__main__":
