@@ -7,7 +7,7 @@ HungarianAllocator.allocate_tasks).  No simulation logic lives in Python.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -21,6 +21,43 @@ F = {name: i for i, name in enumerate([
     "AGENT_TYPE", "AGENT_NAME_IDX", "AGENT_DIST", "AGENT_MISC", "TASK_ID", "TASK_STATUS", "TASK_POS", "TASK_CUR",
     "TASK_ALLOC", "TASK_ORG_DONE", "TASK_META", "TASK_TIMES", "KNOWN", "THREAT_POS", "THREAT_META", "SCALARS",
     "OPEN_IDS", "EVENTS", "EVENT_LIST", "STAGED_ACTIONS", "ERROR", "RELEASE_LOG", "KNOWN_COUNT", "ESCORTS"])}
+
+
+class PolicyKind(NamedTuple):
+    """One learned MLP policy the device runs: the Python mirror of PolPair / PolContextPair / PolCoalition in csrc/muavta_device.h
+    (`with_policy` there maps a kind to its instantiation; the plan gate, the flags and the commit locks live there alone)."""
+    name: str                # 'kind' of a parsed policy
+    label: str               # in messages
+    hidden: int
+    cols: dict               # raw_features as the C struct takes it -> columns of pair_mlp.0.weight
+    max_tasks: int           # the grid of pair_scores is 16 x max_tasks
+    struct: str              # native.<struct>, the argument of libmuavta's <setter>
+    setter: str
+    alias: Optional[str]     # the set_allocator name that runs this kind only ('mlp_pair' runs whichever is installed)
+    source: str              # what set_pair_policy takes for it, in messages
+
+    def w0_text(self):
+        """what pair_mlp.0.weight must look like, in messages (MLP-Pair keeps the wording it had when it was the only kind)"""
+        h, widths = ("hidden", "expected ") if self.name == "pair" else (self.hidden, f"an {self.label} has ")
+        widths += f"[{h}, {next(iter(self.cols.values()))}]"
+        return widths + (f" (raw_features: [{h}, {self.cols[True]}])" if True in self.cols else "")
+
+    def hidden_text(self):
+        return f"hidden = {self.hidden}" if self.name == "pair" else f"{self.label} with hidden = {self.hidden}"
+
+
+POLICY_KINDS = {k.name: k for k in (
+    # PairCostHybrid(use_attention=False).plan under _should_replan(env, events, replan_interval): pair tokens 16 x 32, tanh scores times
+    # score_clamp (experiments/wps_eval.py:244-254 with interval 15, train_pair_cost.py:73-93 with 20)
+    PolicyKind("pair", "MLP-Pair", 128, {False: 25, True: 20}, 32, "MuavtaPairMlp", "muavta_set_pair_policy", None, "a PairCostHybrid checkpoint"),
+    # ContextPairHybrid(use_attention=False): the same plan over cat([agent, task, a_pool, t_pool, context]); ctx_mlp.* / value_mlp.* feed the
+    # value head only and are ignored
+    PolicyKind("context", "MLP-ContextPair", 192, {False: 58, True: 41}, 32, "MuavtaContextPairMlp", "muavta_set_context_pair_policy", "mlp_context_pair",
+               "a ContextPairHybrid checkpoint"),
+    # AttentionEscort(use_attention=False).plan under escort_eval._should_replan: escort tokens 16 x 48 (raw_features = MUAVTA_TOK_ESCORT),
+    # sigmoid scores, commit locks; score_clamp plays no part, value_mlp.* is ignored (experiments/escort_eval.py:181-188 with interval 12)
+    PolicyKind("coalition", "MLP-Coalition", 256, {2: 38}, 48, "MuavtaPairMlp", "muavta_set_pair_policy", "mlp_coalition",
+               "an AttentionEscort(use_attention=False) checkpoint"))}
 
 
 def _vp(a: Optional[np.ndarray]):
@@ -52,6 +89,7 @@ class BatchedMultiUAVEnv:
         self.max_tasks = d.max_tasks
         self.possible_agents = self.params.possible_agents
         self._alloc_mode = 0
+        self._pair_policy = None   # what set_pair_policy last installed (parse_pair_policy's dict)
         self.escalated = {}     # rollout(escalate=True): env index -> (handle of the larger tile, row)
         self._esc_rows = None
 
@@ -120,59 +158,31 @@ class BatchedMultiUAVEnv:
         experiments/wps_eval.py:160-167; replan_interval is ignored) or 'pi' (Local-PI: PerformanceImpact with
         max_tasks_per_agent=1 under its own should_replan gate, replan_interval = its interval; wps_eval.py:147-159).  In the
         two baseline modes rollout_record raises MuavtaError.
-        'mlp_pair' (MLP-Pair: PairCostHybrid(use_attention=False).plan under _should_replan(env, events, replan_interval), the
-        network's forward pass inside the kernel; wps_eval.py:244-254 with interval 15, train_pair_cost.py:73-93 with 20) needs
-        `set_pair_policy` first; rollout_record raises MuavtaError in it too.  The mode runs whatever learned pair policy is
-        installed, MLP-Pair or MLP-ContextPair (ContextPairHybrid(use_attention=False)); 'mlp_context_pair' is the same mode and
-        raises unless the installed policy is an MLP-ContextPair — a check on this object's record of its last `set_pair_policy`, not on the
-        handle: a policy installed or cleared through the C entry points directly is not seen by it.
-        'mlp_coalition' (MLP-Coalition: AttentionEscort(use_attention=False).plan under escort_eval._should_replan(env, events,
-        replan_interval) — escort tokens 16 x 48, sigmoid scores, commit locks; experiments/escort_eval.py:181-188 with interval 12) is
-        the same mode again and raises unless the recorded policy is an MLP-Coalition."""
+        'mlp_pair' runs whatever learned policy `set_pair_policy` installed (a kind of `POLICY_KINDS`: its forward pass inside the kernel,
+        under that kind's gate with replan_interval) and needs one installed first; rollout_record raises MuavtaError in it too.
+        'mlp_context_pair' and 'mlp_coalition' are the same mode and raise unless the installed policy is of their kind — a check on this
+        object's record of its last `set_pair_policy`, not on the handle: a policy installed or cleared through the C entry points
+        directly is not seen by it."""
         mode = self.ALLOCATORS[name]
-        if name == "mlp_coalition" and (getattr(self, "_pair_policy", None) or {}).get("kind") != "coalition":
-            raise MuavtaError("set_allocator('mlp_coalition'): no MLP-Coalition policy is installed (set_pair_policy with an AttentionEscort(use_attention=False) checkpoint first)")
-        if name == "mlp_context_pair" and (getattr(self, "_pair_policy", None) or {}).get("kind") != "context":
-            raise MuavtaError("set_allocator('mlp_context_pair'): no MLP-ContextPair policy is installed (set_pair_policy with a ContextPairHybrid checkpoint first)")
+        need = next((k for k in POLICY_KINDS.values() if k.alias == name), None)
+        if need is not None and self._policy_kind() is not need:
+            raise MuavtaError(f"set_allocator('{name}'): no {need.label} policy is installed (set_pair_policy with {need.source} first)")
         self._ck(self.L.muavta_set_allocator(self.h, mode))
         self._alloc_mode = mode
 
     ALLOCATORS = {"hungarian": 0, "urgency_pair": 1, "urgency_coalition": 2, "hungarian_gated": 3, "cap_greedy": 4, "pi": 5, "mlp_pair": 6,
                   "mlp_context_pair": 6, "mlp_coalition": 6}
     PAIR_MLP_KEYS = tuple(f"pair_mlp.{i}.{k}" for i in (0, 2, 4) for k in ("weight", "bias"))
+    _W = ("w0", "b0", "w1", "b1", "w2", "b2")
+
+    def _policy_kind(self):
+        """the entry of the policy this object last installed (getattr: the no-device tests build the object with __new__)"""
+        return POLICY_KINDS.get((getattr(self, "_pair_policy", None) or {}).get("kind"))
 
     @classmethod
-    def parse_pair_policy(cls, src, score_clamp: Optional[float] = None):
-        """The MLP-Pair network of `src` as {'w0','b0','w1','b1','w2','b2': C-contiguous float32 arrays in state_dict layout,
-        'raw_features': bool, 'score_clamp': float, 'hidden': int}.  `src`: a path to a PairCostHybrid.save checkpoint (torch is
-        imported only then), a state_dict-like mapping with pair_mlp.{0,2,4}.{weight,bias} (torch tensors or arrays; an optional
-        'raw_features' / 'score_clamp' entry is honoured; a mapping with a 'state_dict' entry is a loaded checkpoint), or a PairCostHybrid.
-        Attention checkpoints (use_attention=True / AttPairNet) are refused.  Needs no device.
-        An MLP-ContextPair — a ContextPairHybrid.save checkpoint (kind == 'MLPContextPair'), a ContextPairHybrid(use_attention=False), or
-        a mapping whose pair_mlp.0.weight is [192, 58] (raw_features: [192, 41]) — is returned with 'kind': 'context' and 'hidden': 192
-        (an MLP-Pair with 'kind': 'pair'); its ctx_mlp.* / value_mlp.* entries feed the value head only and are ignored.
-        Att-ContextPair / GNN checkpoints are refused.
-        An MLP-Coalition — an AttentionEscort.save checkpoint (use_attention False, version 2, max_tasks 48, max_agents 16; hidden 256 by
-        its weights), an AttentionEscort(use_attention=False), or a mapping whose pair_mlp.0.weight is [256, 38] — is returned with 'kind':
-        'coalition', 'hidden': 256 and 'raw_features': 2 (the MUAVTA_TOK_ESCORT kind its tokens have); value_mlp.* is ignored and
-        score_clamp plays no part.  Att-Coalition is refused."""
+    def _policy_source(cls, src):
+        """`src` of `parse_pair_policy` -> (state dict, what the source says about itself)"""
         import os
-        raw, clamp, sd = None, None, None
-        coalition = False
-        if hasattr(src, "net") and hasattr(src, "use_attention") and hasattr(src, "commit_threshold") and not hasattr(src, "raw_features"):  # an AttentionEscort
-            src = {"state_dict": src.net.state_dict(), "use_attention": bool(src.use_attention), "max_tasks": int(src.max_tasks),
-                   "max_agents": int(src.max_agents), "version": 2}
-        if hasattr(src, "keys") and "state_dict" in src.keys() and "version" in src.keys() and "raw_features" not in src.keys():  # AttentionEscort.save
-            if src.get("use_attention", True):
-                raise ValueError("set_pair_policy: an Att-Coalition policy (AttentionEscort with use_attention=True) is not supported; only MLP-Coalition runs on the device")
-            for key, want in (("version", 2), ("max_tasks", 48), ("max_agents", 16)):
-                if int(src.get(key, -1)) != want:
-                    raise ValueError(f"set_pair_policy: the MLP-Coalition checkpoint has {key} = {src.get(key)}; the device runs {key} = {want} only")
-            coalition = True
-        ck_kind = getattr(src, "kind", None) if hasattr(src, "net") else (src.get("kind") if hasattr(src, "keys") and "state_dict" in src.keys() else None)
-        if isinstance(ck_kind, str) and (ck_kind == "AttContextPair" or ck_kind.startswith("GNN")):
-            raise ValueError(f"set_pair_policy: a {ck_kind} policy is not supported; of the ContextPair hybrids only MLP-ContextPair runs on the device "
-                             "(Att-ContextPair and GNN-ContextPair do not)")
         if isinstance(src, (str, bytes, os.PathLike)):
             import torch
             try:  # PairCostHybrid.save writes a plain dict of tensors and scalars: nothing in it needs the unpickler to run code
@@ -180,91 +190,113 @@ class BatchedMultiUAVEnv:
             except Exception as exc:
                 raise ValueError(f"set_pair_policy: {src!r} is not a checkpoint of tensors and plain values (torch.load(weights_only=True): {exc}); "
                                  "load it yourself and pass the state_dict") from exc
-            return cls.parse_pair_policy(src, score_clamp)
-        if hasattr(src, "net") and hasattr(src, "use_attention"):  # a PairCostHybrid
-            if src.use_attention:
-                raise ValueError("set_pair_policy: use_attention=True (AttPairNet) is not supported; only the MLP variant runs on the device")
-            raw, clamp, sd = bool(src.raw_features), float(src.score_clamp), src.net.state_dict()
-        elif hasattr(src, "keys") and "state_dict" in src.keys():  # what PairCostHybrid.save writes (PairCostHybrid.py:469-485)
-            if src.get("use_attention", False):
-                raise ValueError("set_pair_policy: the checkpoint was saved with use_attention=True (AttPairNet); only the MLP variant runs on the device")
-            raw, sd = bool(src.get("raw_features", False)), src["state_dict"]
-            clamp = float(src["score_clamp"]) if "score_clamp" in src.keys() else None
-        elif hasattr(src, "keys"):
-            sd = src
-            if "raw_features" in sd.keys():
-                raw = bool(np.asarray(sd["raw_features"]).reshape(-1)[0])
-            if "score_clamp" in sd.keys():
-                clamp = float(np.asarray(sd["score_clamp"]).reshape(-1)[0])
-        else:
-            raise ValueError("set_pair_policy: expected a checkpoint path, a state_dict-like mapping or a PairCostHybrid")
+            return cls._policy_source(src)
+        meta = {"raw": None, "clamp": None, "ck_kind": None, "use_attention": False, "escort": None, "saved": True}
+        if hasattr(src, "net") and hasattr(src, "use_attention"):  # the hybrid itself: read as the checkpoint its .save writes
+            if hasattr(src, "commit_threshold") and not hasattr(src, "raw_features"):  # an AttentionEscort
+                own = {"version": 2, "max_tasks": int(src.max_tasks), "max_agents": int(src.max_agents)}
+            else:  # a PairCostHybrid / ContextPairHybrid
+                own = {"kind": getattr(src, "kind", None), "raw_features": src.raw_features, "score_clamp": src.score_clamp}
+            src, meta["saved"] = {"state_dict": src.net.state_dict(), "use_attention": bool(src.use_attention), **own}, False
+        if hasattr(src, "keys") and "state_dict" in src.keys():  # what PairCostHybrid.save (PairCostHybrid.py:469-485) or AttentionEscort.save writes
+            escort = "version" in src.keys() and "raw_features" not in src.keys()
+            meta.update(use_attention=bool(src.get("use_attention", escort)), ck_kind=src.get("kind"), raw=bool(src.get("raw_features", False)))
+            if escort:
+                meta["escort"] = {key: src.get(key) for key in ("version", "max_tasks", "max_agents")}
+            if "score_clamp" in src.keys():
+                meta["clamp"] = float(src["score_clamp"])
+            return src["state_dict"], meta
+        if hasattr(src, "keys"):
+            for key, name, cast in (("raw_features", "raw", bool), ("score_clamp", "clamp", float)):
+                if key in src.keys():
+                    meta[name] = cast(np.asarray(src[key]).reshape(-1)[0])
+            return src, meta
+        raise ValueError("set_pair_policy: expected a checkpoint path, a state_dict-like mapping or a PairCostHybrid")
+
+    @classmethod
+    def _classify_policy(cls, sd, meta):
+        """-> (entry of POLICY_KINDS, the six arrays), or ValueError for what the device does not run.  The source's own markers decide
+        first — an AttentionEscort checkpoint is a coalition, kind == 'MLPContextPair' a context, any other kind a pair — then the columns
+        of layer 1; a net whose columns belong to another kind than its marker is refused, not re-read as that kind."""
+        pair, context, coalition = (POLICY_KINDS[k] for k in ("pair", "context", "coalition"))
+        escort, ck = meta["escort"], meta["ck_kind"]
+        if escort is not None:
+            if meta["use_attention"]:
+                raise ValueError("set_pair_policy: an Att-Coalition policy (AttentionEscort with use_attention=True) is not supported; only MLP-Coalition runs on the device")
+            for key, want in (("version", 2), ("max_tasks", coalition.max_tasks), ("max_agents", 16)):
+                if escort[key] is None or int(escort[key]) != want:
+                    raise ValueError(f"set_pair_policy: the MLP-Coalition checkpoint has {key} = {escort[key]}; the device runs {key} = {want} only")
+        if isinstance(ck, str) and (ck == "AttContextPair" or ck.startswith("GNN")):
+            raise ValueError(f"set_pair_policy: a {ck} policy is not supported; of the ContextPair hybrids only MLP-ContextPair runs on the device "
+                             "(Att-ContextPair and GNN-ContextPair do not)")
+        if meta["use_attention"]:
+            raise ValueError("set_pair_policy: the checkpoint was saved with use_attention=True (AttPairNet); only the MLP variant runs on the device" if meta["saved"]
+                             else "set_pair_policy: use_attention=True (AttPairNet) is not supported; only the MLP variant runs on the device")
         missing = [k for k in cls.PAIR_MLP_KEYS if k not in sd.keys()]
         if missing:
             att = any(str(k).startswith(("encoder", "task_proj", "agent_proj", "cross")) for k in sd.keys())
             raise ValueError(f"set_pair_policy: no {missing[0]} in the weights" + (" (an attention net? only the MLP variant is supported)" if att else ""))
+        tensors = (sd[k] for k in cls.PAIR_MLP_KEYS)
+        arrays = [np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32) for v in tensors]
+        w0 = arrays[0]
+        allowed = (coalition,) if escort is not None else (context,) if ck == "MLPContextPair" else (pair, context, coalition) if ck is None else (pair,)
+        for kind in allowed:
+            if w0.ndim == 2 and w0.shape[1] in kind.cols.values():
+                return kind, arrays
+        raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {w0.shape}; {(coalition if escort is not None else pair).w0_text()}")
 
-        def arr(k):
-            v = sd[k]
-            if hasattr(v, "detach"):
-                v = v.detach().cpu().numpy()
-            return np.ascontiguousarray(v, dtype=np.float32)
-        w0, b0, w1, b1, w2, b2 = (arr(k) for k in cls.PAIR_MLP_KEYS)
-        hidden = b0.shape[0] if b0.ndim == 1 else -1
-        coalition = coalition or (w0.ndim == 2 and w0.shape[1] == 38 and ck_kind is None)
-        if coalition:  # MLPCoalitionNet.pair_mlp: agent 16 + task 22 columns
-            if w0.ndim != 2 or w0.shape[1] != 38:
-                raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {w0.shape}; an MLP-Coalition has [256, 38]")
-            if hidden != 256:
-                raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's MLP-Coalition with hidden = 256 only")
-        context = not coalition and w0.ndim == 2 and w0.shape[1] in (41, 58) and ck_kind in (None, "MLPContextPair")
-        if coalition:
-            raw = 2
-        elif context:  # MLPContextPairNet.pair_mlp: agent, task, a_pool, t_pool, context columns
-            if raw is not None and w0.shape[1] != (41 if raw else 58):
-                raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {w0.shape}; an MLP-ContextPair has [192, 58] (raw_features: [192, 41])")
-            raw = w0.shape[1] == 41
-        elif w0.ndim != 2 or w0.shape[1] not in (20, 25) or (raw is not None and w0.shape[1] != (20 if raw else 25)) or ck_kind == "MLPContextPair":
-            raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {w0.shape}; expected [hidden, 25] (raw_features: [hidden, 20])")
-        else:
-            raw = w0.shape[1] == 20
-        want = {"pair_mlp.0.weight": (hidden, w0.shape[1]), "pair_mlp.0.bias": (hidden,), "pair_mlp.2.weight": (hidden, hidden),
-                "pair_mlp.2.bias": (hidden,), "pair_mlp.4.weight": (1, hidden), "pair_mlp.4.bias": (1,)}
-        for k, a in zip(cls.PAIR_MLP_KEYS, (w0, b0, w1, b1, w2, b2)):
-            if a.shape != want[k]:
-                raise ValueError(f"set_pair_policy: {k} has shape {a.shape}; expected {want[k]}")
-        if coalition:
-            pass
-        elif context and hidden != 192:
-            raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's MLP-ContextPair with hidden = 192 only")
-        elif not context and hidden != 128:
-            raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's hidden = 128 only")
-        if score_clamp is not None:
-            clamp = float(score_clamp)
+    @classmethod
+    def parse_pair_policy(cls, src, score_clamp: Optional[float] = None):
+        """The learned policy network of `src` as {'w0','b0','w1','b1','w2','b2': C-contiguous float32 arrays in state_dict layout,
+        'raw_features': what the C struct takes, 'score_clamp': float, 'hidden': int, 'kind': a key of `POLICY_KINDS`}.  `src`: a path to a
+        checkpoint the reference's .save wrote (torch is imported only then), a loaded checkpoint (a mapping with a 'state_dict' entry), a
+        state_dict-like mapping with pair_mlp.{0,2,4}.{weight,bias} (torch tensors or arrays; an optional 'raw_features' / 'score_clamp'
+        entry is honoured), or the hybrid object itself.  `POLICY_KINDS` lists the kinds with their hidden size and layer 1's columns, by
+        which a bare mapping is told apart; attention and GNN variants are refused.  Needs no device."""
+        sd, meta = cls._policy_source(src)
+        kind, arrays = cls._classify_policy(sd, meta)
+        hidden, cols = arrays[1].shape[0] if arrays[1].ndim == 1 else -1, arrays[0].shape[1]
+        if kind.cols.get(meta["raw"], cols) != cols:  # (a kind without a raw variant has no entry for the source's bool: nothing to contradict)
+            raise ValueError(f"set_pair_policy: pair_mlp.0.weight has shape {arrays[0].shape}; {kind.w0_text()}")
+        def shapes():
+            want = ((hidden, cols), (hidden,), (hidden, hidden), (hidden,), (1, hidden), (1,))
+            for k, a, shape in zip(cls.PAIR_MLP_KEYS, arrays, want):
+                if a.shape != shape:
+                    raise ValueError(f"set_pair_policy: {k} has shape {a.shape}; expected {shape}")
+
+        def width():
+            if hidden != kind.hidden:
+                raise ValueError(f"set_pair_policy: hidden = {hidden}; the device runs the reference's {kind.hidden_text()} only")
+        # (a net with two faults keeps the message it always had: an MLP-Coalition was asked for its width first, the others for their shapes)
+        for check in (width, shapes) if kind.name == "coalition" else (shapes, width):
+            check()
+        clamp = float(score_clamp) if score_clamp is not None else meta["clamp"]
         if clamp is None:
             clamp = 0.35  # SCORE_CLAMP (PairCostHybrid.py): the value every checkpoint of the reference is trained and saved with
-        return {"w0": w0, "b0": b0, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "raw_features": raw, "score_clamp": clamp, "hidden": hidden,
-                "kind": "coalition" if coalition else "context" if context else "pair"}
+        return {**dict(zip(cls._W, arrays)), "raw_features": next(r for r, c in kind.cols.items() if c == cols), "score_clamp": clamp,
+                "hidden": hidden, "kind": kind.name}
 
     def set_pair_policy(self, src, score_clamp: Optional[float] = None):
         """muavta_set_pair_policy / muavta_set_context_pair_policy: the network `set_allocator('mlp_pair')` and `pair_scores` run (see
-        `parse_pair_policy` for `src`; None clears it).  The weights are copied; a second call replaces them — of either kind —
+        `parse_pair_policy` for `src`; None clears it).  The weights are copied; a second call replaces them — of any kind —
         also between rollouts."""
-        if src is None:
+        self._install_policy(None if src is None else self.parse_pair_policy(src, score_clamp))
+
+    def _install_policy(self, pol: Optional[dict]):
+        """what `parse_pair_policy` returned, through its kind's setter"""
+        if pol is None:
             self._ck(self.L.muavta_set_pair_policy(self.h, None))
-            self._pair_policy = None
-            return
-        pol = self.parse_pair_policy(src, score_clamp)
-        context = pol["kind"] == "context"
-        spec = (native.MuavtaContextPairMlp if context else native.MuavtaPairMlp)(
-            int(pol["raw_features"]), int(pol["hidden"]), float(pol["score_clamp"]), *(pol[k].ctypes.data for k in ("w0", "b0", "w1", "b1", "w2", "b2")))
-        self._ck((self.L.muavta_set_context_pair_policy if context else self.L.muavta_set_pair_policy)(self.h, C.byref(spec)))
+        else:
+            kind = POLICY_KINDS[pol["kind"]]
+            spec = getattr(native, kind.struct)(int(pol["raw_features"]), int(pol["hidden"]), float(pol["score_clamp"]), *(pol[k].ctypes.data for k in self._W))
+            self._ck(getattr(self.L, kind.setter)(self.h, C.byref(spec)))
         self._pair_policy = pol
 
     def pair_scores(self, out=None, want_logits: bool = False):
         """muavta_pair_scores: the policy's scores (and logits) f32 [N, 16, 32] ([N, 16, 48] while the recorded policy is an
         MLP-Coalition) of every env's current state, 0 where edge_valid is 0.  numpy by default (synchronises); `out` = {'scores': t[, 'logits': t]} of contiguous CUDA torch tensors goes through
         the device entry on the handle's stream without a sync and is returned."""
-        shape = (self.n_envs, 16, 48 if (getattr(self, "_pair_policy", None) or {}).get("kind") == "coalition" else 32)
+        shape = (self.n_envs, 16, (self._policy_kind() or POLICY_KINDS["pair"]).max_tasks)
         if out is not None:
             if not out:
                 raise ValueError("pair_scores: out must hold a 'scores' and / or a 'logits' tensor")
@@ -574,10 +606,8 @@ class BatchedMultiUAVEnv:
                 p.tile_agents, p.tile_tasks, p.tile_threats = a, t, max(hh, self.H)
                 h = BatchedMultiUAVEnv(p, max(len(idx), 64), device=self.device_index)
                 self._esc_handles[rung] = h
-            if getattr(self, "_pair_policy", None) is not None and getattr(h, "_pair_policy_from", None) is not self._pair_policy:  # (new handle, or the policy changed since)
-                h.set_pair_policy({**{k: self._pair_policy[w] for k, w in zip(self.PAIR_MLP_KEYS, ("w0", "b0", "w1", "b1", "w2", "b2"))},
-                                   "raw_features": self._pair_policy["raw_features"]}, self._pair_policy["score_clamp"])
-                h._pair_policy_from = self._pair_policy
+            if self._pair_policy is not None and h._pair_policy is not self._pair_policy:  # (new handle, or the policy changed since)
+                h._install_policy(self._pair_policy)
             h._ck(h.L.muavta_set_allocator(h.h, self._alloc_mode))
             s2 = np.full(h.n_envs, seeds[idx[0]], dtype=np.uint64)
             s2[:len(idx)] = seeds[idx]

@@ -3,7 +3,7 @@
   // PairCostHybrid(use_attention=False) (TaskAllocation/Hybrid/PairCostHybrid.py:154-197,266-278,308-328):
   //   logits = pair_mlp(cat([agent_feats[i], task_feats[j]]))     Linear(25|20, 128) - ReLU - Linear(128, 128) - ReLU - Linear(128, 1)
   //   scores = tanh(logits) * score_clamp * edge_valid            -> HungarianAllocator.allocate_tasks(edge_scores=...) = allocate<true>
-  // ARITHMETIC CONTRACT (DESIGN.md §7; tests/pair_mlp_py.py is its host twin).  torch leaves its summation order open, so the device
+  // ARITHMETIC CONTRACT (DESIGN.md §7; tests/policy_mlp_py.py is its host twin).  torch leaves its summation order open, so the device
   // defines its own and keeps to it everywhere:
   //   * every Linear output is ONE k-ascending float32 fmaf chain that starts from the bias:
   //         acc = b[n];  for k = 0 .. K-1:  acc = fmaf(W[n][k], x[k], acc)
@@ -185,7 +185,7 @@
   }
   // ---- MLP-ContextPair: ContextPairHybrid(use_attention=False) (TaskAllocation/Hybrid/ContextPairHybrid.py:154-210) --------------------
   //   pair = cat([agent_feats[i], task_feats[j], a_pool, t_pool, context]);  logits = pair_mlp(pair)   Linear(58|41, 192) - ReLU - Linear(192, 192) - ReLU - Linear(192, 1)
-  // plan(), the tokens, edge_valid, the scored Hungarian and the gate are PairCostHybrid's.  CONTRACT (DESIGN.md §7.1; tests/context_pair_mlp_py.py):
+  // plan(), the tokens, edge_valid, the scored Hungarian and the gate are PairCostHybrid's.  CONTRACT (DESIGN.md §7.1; tests/policy_mlp_py.py):
   //   * pool[d]: s = 0.0f; s = s + x[row][d] in float32 over the rows whose mask is 0, ascending row; pool[d] = s / (float)max(count, 1), IEEE division
   //     (a_pool over the 16 agent rows, t_pool over the 32 task rows); context = what Sim::context(raw, 32, .) writes;
   //   * layer 1: one fmaf chain per output from the bias over a_pool, t_pool, context, the agent row, the task row (each ascending) — the
@@ -220,7 +220,7 @@
   // ---- MLP-Coalition: AttentionEscort(use_attention=False) (TaskAllocation/Hybrid/AttentionEscort.py:326-367,370-524) ---------------------------
   //   logits = pair_mlp(cat([agent_feats[i], task_feats[j]]))      Linear(38, 256) - ReLU - Linear(256, 256) - ReLU - Linear(256, 1)
   //   scores = sigmoid(clip(logits, -20, 20)) * edge_valid * non-pad -> _plan_from_scores: allocate_tasks(force=True, reserved=committed_names,
-  //   edge_scores = every non-pad pair) + apply_agent_commits.  CONTRACT (DESIGN.md §7.1; tests/coalition_mlp_py.py): layer 1 is one chain over the
+  //   edge_scores = every non-pad pair) + apply_agent_commits.  CONTRACT (DESIGN.md §7.1; tests/policy_mlp_py.py): layer 1 is one chain over the
   //   agent row's 16 features, then the task row's 22; layers 2 and 3 as above; score = 1.0f / (1.0f + expf(-fminf(fmaxf(logit, -20.0f), 20.0f)));
   //   pad pairs and pairs whose edge_valid is 0 are not evaluated and score 0; score_clamp is not used.
   // The forward pass of the installed policy over the env's scratch block (a network with env-uniform inputs: after context_prefix())

@@ -1,5 +1,5 @@
 """The learned MLP-Coalition policy on the device (muavta_set_pair_policy with raw_features = MUAVTA_TOK_ESCORT + MUAVTA_ALLOC_MLP_PAIR,
-csrc/sim/policy.inc) against its host twin (tests/coalition_mlp_py.py: the arithmetic contract, bit for bit up to the logits), against the
+csrc/sim/policy.inc) against its host twin (tests/policy_mlp_py.py: the arithmetic contract, bit for bit up to the logits), against the
 reference's recorded episodes (tools/gen_golden_mlp_coalition.py) and against itself along every path that carries the mode (fused rollout,
 stepwise allocate, tokens -> pair_scores -> allocate_scored, lanes, policy swaps).  Tolerances: none on logits and on anything between device
 paths; a score against sigmoid of its own logit in float64 within 4 x 2^-24 (division, expf and the add: about 1 ulp each on values <= 1 —
@@ -11,12 +11,9 @@ import os
 import numpy as np
 import pytest
 
-import coalition_mlp_py as twin
-import context_pair_mlp_py
-import pair_mlp_py
+import policy_mlp_py as twin
 from muavta_amd.native import MuavtaError
-from muavta_amd.params import params_for_case
-from test_gpu_parity import Snapshot
+from test_gpu_mlp_pair import _env, compare_paths, full_state, stepwise
 
 pytestmark = pytest.mark.gpu
 
@@ -29,18 +26,8 @@ INTERVAL = 12
 SCORE_BOUND = 4 * 2.0 ** -24
 
 
-def _env(case, n, **kw):
-    from muavta_amd.batched import BatchedMultiUAVEnv
-    return BatchedMultiUAVEnv(params_for_case(case, **kw), n)
-
-
 def _weights(name):
-    z = np.load(os.path.join(GOLDEN, f"mlpcoal_weights_{name}.npz"))
-    if "base" in z.files:  # layer 3 only, over another set
-        w = _weights(str(z["base"]))
-        w["w2"], w["b2"] = np.ascontiguousarray(z["w2"], np.float32), np.ascontiguousarray(z["b2"], np.float32)
-        return w
-    return twin.load_weights(os.path.join(GOLDEN, f"mlpcoal_weights_{name}.npz"))
+    return twin.load_weights(twin.COALITION, name)
 
 
 def _policy_env(case, n, wname, **kw):
@@ -56,7 +43,7 @@ def check_against_twin(env, w, tag, seen):
     tok = env.tokens("escort", 48, 16)
     scores, logits = env.pair_scores(want_logits=True)
     assert scores.shape == (env.n_envs, 16, 48)
-    ts, tl = twin.forward_batch(w, tok)
+    ts, tl = twin.forward_batch(twin.COALITION, w, tok)
     ev = tok["edge_valid"] != 0
     ok = ev & (tok["agent_mask"] == 0)[:, :, None] & (tok["task_mask"] == 0)[:, None, :]
     assert np.array_equal(ok, ev), f"{tag}: edge_valid set on a pad pair"
@@ -166,25 +153,6 @@ def test_scores_vs_reference_along_its_trajectory(path):
 
 
 # 3. the chain, bit for bit
-def metrics_of(env):
-    m = np.empty((env.n_envs, 30), dtype=np.float64)
-    rc = env.L.muavta_metrics(env.h, m.ctypes.data)
-    assert rc in (0, -4), env.L.muavta_last_error(env.h)  # (MUAVTA_E_CAPACITY: the rows are filled all the same)
-    return m
-
-
-def full_state(env):
-    s = Snapshot(env)
-    d = {n: getattr(s, n) for n in Snapshot.NAMES}  # (AGENT_MISC carries commit_until, SCALARS n_replans)
-    d["metrics"] = metrics_of(env)
-    return d
-
-
-def assert_same(a, b, rows, tag):
-    for k in a:
-        assert np.array_equal(np.asarray(a[k])[rows], np.asarray(b[k])[rows]), f"{tag}: {k}"
-
-
 @pytest.mark.parametrize("case,tile", [("WPS_hard", 16), ("WPS_escort", 24), ("WPS_burst64", 64)])
 def test_fused_equals_stepwise_equals_scored_chain(case, tile):
     """16 envs x 150 steps, interval 12, none with a tolerance (the 24 x 48 tile with WPS_escort: under this policy most WPS_escort24 envs
@@ -202,25 +170,8 @@ def test_fused_equals_stepwise_equals_scored_chain(case, tile):
     A = full_state(fused)
     assert np.array_equal(A["metrics"], rm)
 
-    def stepwise(env, plan):
-        env.reset(seeds)
-        early = np.zeros(n, bool)
-        at_end = {}
-        for t in range(steps):
-            plan(env)
-            env.step_staged()
-            if t < steps - 1:
-                _, term, trunc = env.step_result()
-                new = ((term != 0) | (trunc != 0)) & ~early
-                if new.any():
-                    m, sc, er = metrics_of(env), env.get("SCALARS"), env.get("ERROR")
-                    for i in np.nonzero(new)[0]:
-                        at_end[int(i)] = (m[i].copy(), sc[i].copy(), int(er[i]))
-                    early |= new
-        return full_state(env), early, at_end
-
     step, _ = _policy_env(case, n, "init2")
-    B, early, endB = stepwise(step, lambda e: e.allocate(INTERVAL, True, fetch=False))
+    path_b = stepwise(step, seeds, steps, lambda e: e.allocate(INTERVAL, True, fetch=False))
     chain, _ = _policy_env(case, n, "init2")
     chain.set_allocator("hungarian")  # the scores come through the stand-alone kernel: no allocator mode involved
     sc = torch.empty((n, 16, 48), dtype=torch.float32, device=torch.device("cuda", chain.device_index))
@@ -228,22 +179,9 @@ def test_fused_equals_stepwise_equals_scored_chain(case, tile):
     def plan_chain(e):
         e.pair_scores(out={"scores": sc})
         e.allocate_scored("escort", 48, 16, edge_scores=sc, gate="escort", replan_interval=INTERVAL, use_visibility=True, edge_valid_only=False, commit=True, out={})
-    Cc, early_c, endC = stepwise(chain, plan_chain)
-    assert np.array_equal(early, early_c) and np.array_equal(B["ERROR"], Cc["ERROR"])
-    ok = (A["ERROR"] == 0) & (B["ERROR"] == 0)
-    assert np.array_equal(A["ERROR"][~early] != 0, B["ERROR"][~early] != 0)
-    assert_same(B, Cc, ok, f"{case} stepwise vs scored chain")
-    assert_same(A, B, ok & ~early, f"{case} fused vs stepwise")
-    n_early = 0
-    for i in np.nonzero(early)[0]:
-        mb, sb, eb = endB[int(i)]
-        mc, scc, ec = endC[int(i)]
-        assert eb == ec and np.array_equal(mb, mc) and np.array_equal(sb, scc), f"{case} env {i}: stepwise vs scored chain at the episode's end"
-        if eb == 0 and A["ERROR"][i] == 0:
-            assert np.array_equal(A["metrics"][i], mb) and np.array_equal(A["SCALARS"][i], sb), f"{case} env {i}: fused vs stepwise at the episode's end"
-            n_early += 1
-    compared = int((ok & ~early).sum()) + n_early
-    print(f"{case} interval {INTERVAL}: {n} envs, {int((ok & ~early).sum())} compared in full at step {steps}, {n_early} at their earlier end, {n - compared} outgrew the tile; "
+    full, n_early = compare_paths(case, A, path_b, stepwise(chain, seeds, steps, plan_chain))
+    compared = full + n_early
+    print(f"{case} interval {INTERVAL}: {n} envs, {full} compared in full at step {steps}, {n_early} at their earlier end, {n - compared} outgrew the tile; "
           f"mean n_replans {A['SCALARS'][:, 23].mean():.1f}")
     assert compared >= 12, f"only {compared} of {n} envs could be compared"
     assert A["SCALARS"][:, 23].max() >= 5  # plans were made
@@ -318,8 +256,8 @@ def test_swapping_pair_coalition_context_coalition_between_rollouts():
     result equal to a fresh handle's — the coalition kind's scratch block is created on the way and survives the other kinds."""
     case, n = "WPS_escort", 16
     seeds = np.arange(n, dtype=np.uint64) + 7
-    sd_p = pair_mlp_py.as_state_dict(pair_mlp_py.load_weights(os.path.join(GOLDEN, "mlppair_weights_init2.npz")))
-    sd_x = context_pair_mlp_py.as_state_dict(context_pair_mlp_py.load_weights(os.path.join(GOLDEN, "mlpctx_weights_init2.npz")))
+    sd_p = twin.as_state_dict(twin.load_weights(twin.PAIR, "init2"))
+    sd_x = twin.as_state_dict(twin.load_weights(twin.CONTEXT, "init2"))
     sd_c = twin.as_state_dict(_weights("init2"))
 
     def fresh(sd, interval):

@@ -1,5 +1,5 @@
 """The learned MLP-ContextPair policy on the device (muavta_set_context_pair_policy + MUAVTA_ALLOC_MLP_PAIR, csrc/sim/policy.inc) against its
-host twin (tests/context_pair_mlp_py.py: the arithmetic contract, bit for bit up to the logits), against the reference's recorded episodes
+host twin (tests/policy_mlp_py.py: the arithmetic contract, bit for bit up to the logits), against the reference's recorded episodes
 (tools/gen_golden_mlp_context_pair.py) and against itself along every path that carries the mode (fused rollout, stepwise allocate,
 pair_scores -> allocate_scored, parts, lanes, policy swaps).  Tolerances: none on logits and on anything between device paths; scores
 against the reference's float64 evaluation within 4 x D_ref of the trace, D_ref = the reference's own float32 deviation from that
@@ -10,11 +10,9 @@ import os
 import numpy as np
 import pytest
 
-import context_pair_mlp_py as twin
-import pair_mlp_py
+import policy_mlp_py as twin
 from muavta_amd.native import MuavtaError
-from muavta_amd.params import params_for_case
-from test_gpu_parity import Snapshot
+from test_gpu_mlp_pair import _env, compare_paths, full_state, stepwise
 
 pytestmark = pytest.mark.gpu
 
@@ -25,17 +23,12 @@ TILE_CASES = [("WPS_hard", 16), ("WPS_escort24", 24), ("WPS_burst64", 64)]
 BOUND = 4.0  # x D_ref
 
 
-def _env(case, n, **kw):
-    from muavta_amd.batched import BatchedMultiUAVEnv
-    return BatchedMultiUAVEnv(params_for_case(case, **kw), n)
-
-
 def _weights(name):
-    return twin.load_weights(os.path.join(GOLDEN, f"mlpctx_weights_{name}.npz"))
+    return twin.load_weights(twin.CONTEXT, name)
 
 
 def _pair_weights(name):
-    return pair_mlp_py.load_weights(os.path.join(GOLDEN, f"mlppair_weights_{name}.npz"))
+    return twin.load_weights(twin.PAIR, name)
 
 
 def _policy_env(case, n, wname, **kw):
@@ -55,7 +48,7 @@ def check_against_twin(env, w, tag, seen):
     tok = env.tokens(_kind(w), 32, 16)
     ctx = env.context(_kind(w), 32)
     scores, logits = env.pair_scores(want_logits=True)
-    ts, tl = twin.forward_batch(w, tok, ctx)
+    ts, tl = twin.forward_batch(twin.CONTEXT, w, dict(tok, context=ctx))
     ev = tok["edge_valid"] != 0
     diff = logits.view(np.uint32) != tl.view(np.uint32)
     assert not diff.any(), f"{tag}: {int(diff.sum())} of {int(ev.sum())} logits differ from the host twin"
@@ -132,7 +125,7 @@ def test_tanhf_over_its_range():
         if t % 15 == 0:
             tok, ctx = env.tokens("pair", 32, 16), env.context("pair", 32)
             scores, logits = env.pair_scores(want_logits=True)
-            _, tl = twin.forward_batch(w, tok, ctx)
+            _, tl = twin.forward_batch(twin.CONTEXT, w, dict(tok, context=ctx))
             ev = tok["edge_valid"] != 0
             assert np.array_equal(logits.view(np.uint32), tl.view(np.uint32))
             want = np.tanh(logits.astype(np.float64)) * np.float64(np.float32(w["score_clamp"]))
@@ -192,25 +185,6 @@ def test_scores_vs_reference_along_its_trajectory(path):
 
 
 # 3. the chain, bit for bit
-def metrics_of(env):
-    m = np.empty((env.n_envs, 30), dtype=np.float64)
-    rc = env.L.muavta_metrics(env.h, m.ctypes.data)
-    assert rc in (0, -4), env.L.muavta_last_error(env.h)  # (MUAVTA_E_CAPACITY: the rows are filled all the same)
-    return m
-
-
-def full_state(env):
-    s = Snapshot(env)
-    d = {n: getattr(s, n) for n in Snapshot.NAMES}
-    d["metrics"] = metrics_of(env)
-    return d
-
-
-def assert_same(a, b, rows, tag):
-    for k in a:
-        assert np.array_equal(np.asarray(a[k])[rows], np.asarray(b[k])[rows]), f"{tag}: {k}"
-
-
 @pytest.mark.parametrize("case,tile,interval,use_vis,wname", [("WPS_hard", 16, 15, True, "init2"), ("WPS_escort24", 24, 20, False, "init2_raw"),
                                                               ("WPS_burst64", 64, 20, True, "il3")])
 def test_fused_equals_stepwise_equals_scored_chain(case, tile, interval, use_vis, wname):
@@ -228,25 +202,8 @@ def test_fused_equals_stepwise_equals_scored_chain(case, tile, interval, use_vis
     A = full_state(fused)
     assert np.array_equal(A["metrics"], rm)
 
-    def stepwise(env, plan):
-        env.reset(seeds)
-        early = np.zeros(n, bool)
-        at_end = {}
-        for t in range(steps):
-            plan(env)
-            env.step_staged()
-            if t < steps - 1:
-                _, term, trunc = env.step_result()
-                new = ((term != 0) | (trunc != 0)) & ~early
-                if new.any():
-                    m, sc, er = metrics_of(env), env.get("SCALARS"), env.get("ERROR")
-                    for i in np.nonzero(new)[0]:
-                        at_end[int(i)] = (m[i].copy(), sc[i].copy(), int(er[i]))
-                    early |= new
-        return full_state(env), early, at_end
-
     step, _ = _policy_env(case, n, wname)
-    B, early, endB = stepwise(step, lambda e: e.allocate(interval, use_vis, fetch=False))
+    path_b = stepwise(step, seeds, steps, lambda e: e.allocate(interval, use_vis, fetch=False))
     chain, _ = _policy_env(case, n, wname)
     chain.set_allocator("hungarian")  # the scores come through the stand-alone kernel: no allocator mode involved
     sc = torch.empty((n, 16, 32), dtype=torch.float32, device=torch.device("cuda", chain.device_index))
@@ -254,22 +211,9 @@ def test_fused_equals_stepwise_equals_scored_chain(case, tile, interval, use_vis
     def plan_chain(e):
         e.pair_scores(out={"scores": sc})
         e.allocate_scored(_kind(w), 32, 16, edge_scores=sc, gate="trainer", replan_interval=interval, use_visibility=use_vis, edge_valid_only=True, out={})
-    Cc, early_c, endC = stepwise(chain, plan_chain)
-    assert np.array_equal(early, early_c) and np.array_equal(B["ERROR"], Cc["ERROR"])
-    ok = (A["ERROR"] == 0) & (B["ERROR"] == 0)
-    assert np.array_equal(A["ERROR"][~early] != 0, B["ERROR"][~early] != 0)
-    assert_same(B, Cc, ok, f"{case} stepwise vs scored chain")
-    assert_same(A, B, ok & ~early, f"{case} fused vs stepwise")
-    n_early = 0
-    for i in np.nonzero(early)[0]:
-        mb, sb, eb = endB[int(i)]
-        mc, scc, ec = endC[int(i)]
-        assert eb == ec and np.array_equal(mb, mc) and np.array_equal(sb, scc), f"{case} env {i}: stepwise vs scored chain at the episode's end"
-        if eb == 0 and A["ERROR"][i] == 0:
-            assert np.array_equal(A["metrics"][i], mb) and np.array_equal(A["SCALARS"][i], sb), f"{case} env {i}: fused vs stepwise at the episode's end"
-            n_early += 1
-    compared = int((ok & ~early).sum()) + n_early
-    print(f"{case} {wname} interval {interval} vis {use_vis}: {n} envs, {int((ok & ~early).sum())} compared in full at step {steps}, {n_early} at their earlier end, "
+    full, n_early = compare_paths(case, A, path_b, stepwise(chain, seeds, steps, plan_chain))
+    compared = full + n_early
+    print(f"{case} {wname} interval {interval} vis {use_vis}: {n} envs, {full} compared in full at step {steps}, {n_early} at their earlier end, "
           f"{n - compared} outgrew the tile")
     assert (n - compared) * 16 <= n, f"{n - compared} of {n} envs outgrew the tile"
     assert A["SCALARS"][:, 23].max() >= 5  # plans were made
@@ -374,16 +318,16 @@ def test_swapping_pair_context_pair_between_rollouts():
         e.set_allocator("mlp_pair")
         e.rollout(seeds, 150, 15, True, True)
         return e.rollout_metrics(), e.pair_scores()
-    want_p, sc_p = fresh(pair_mlp_py.as_state_dict(wp))
+    want_p, sc_p = fresh(twin.as_state_dict(wp))
     want_c, sc_c = fresh(twin.as_state_dict(wc))
     assert not np.array_equal(want_p, want_c) and not np.array_equal(sc_p, sc_c)
     env = _env(case, n)
     env.set_lanes(2)
-    env.set_pair_policy(pair_mlp_py.as_state_dict(wp))
+    env.set_pair_policy(twin.as_state_dict(wp))
     env.set_allocator("mlp_pair")
     with pytest.raises(MuavtaError, match="MLP-ContextPair"):
         env.set_allocator("mlp_context_pair")
-    for sd, want, sc in ((pair_mlp_py.as_state_dict(wp), want_p, sc_p), (twin.as_state_dict(wc), want_c, sc_c), (pair_mlp_py.as_state_dict(wp), want_p, sc_p)):
+    for sd, want, sc in ((twin.as_state_dict(wp), want_p, sc_p), (twin.as_state_dict(wc), want_c, sc_c), (twin.as_state_dict(wp), want_p, sc_p)):
         env.set_pair_policy(sd)
         env.rollout(seeds, 150, 15, True, True)
         assert np.array_equal(env.rollout_metrics(), want)

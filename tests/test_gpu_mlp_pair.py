@@ -1,4 +1,4 @@
-"""The learned MLP-Pair hybrid on the device (MUAVTA_ALLOC_MLP_PAIR, csrc/sim/policy.inc) against its host twin (tests/pair_mlp_py.py:
+"""The learned MLP-Pair hybrid on the device (MUAVTA_ALLOC_MLP_PAIR, csrc/sim/policy.inc) against its host twin (tests/policy_mlp_py.py:
 the arithmetic contract, bit for bit up to the logits), against the reference's recorded episodes (tools/gen_golden_mlp_pair.py) and
 against itself along every path that carries the mode (fused rollout, stepwise allocate, pair_scores -> allocate_scored, parts, lanes,
 escalation).  Tolerances: none on logits and on anything between device paths; scores against the reference's float64 evaluation within
@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-import pair_mlp_py as twin
+import policy_mlp_py as twin
 from muavta_amd.native import MuavtaError
 from muavta_amd.params import params_for_case
 from test_gpu_parity import Snapshot
@@ -29,7 +29,7 @@ def _env(case, n, **kw):
 
 
 def _weights(name):
-    return twin.load_weights(os.path.join(GOLDEN, f"mlppair_weights_{name}.npz"))
+    return twin.load_weights(twin.PAIR, name)
 
 
 def _policy_env(case, n, wname, **kw):
@@ -56,23 +56,10 @@ def d_ref_of(wname):
     return worst
 
 
-def twin_batch(w, tok):
-    """the host twin over every env of a token dict at once: (scores, logits) [N, 16, 32]"""
-    ev = tok["edge_valid"] != 0
-    nn, ii, jj = np.nonzero(ev)
-    logits = np.zeros(ev.shape, np.float32)
-    scores = np.zeros(ev.shape, np.float32)
-    if len(nn):
-        lg = twin.pair_logits(w, np.concatenate([tok["agent_feats"][nn, ii], tok["task_feats"][nn, jj]], axis=1))
-        logits[nn, ii, jj] = lg
-        scores[nn, ii, jj] = (np.tanh(lg) * np.float32(w["score_clamp"])).astype(np.float32)
-    return scores, logits
-
-
 def check_against_twin(env, w, tag):
     tok = env.tokens(_kind(w), 32, 16)
     scores, logits = env.pair_scores(want_logits=True)
-    ts, tl = twin_batch(w, tok)
+    ts, tl = twin.forward_batch(twin.PAIR, w, tok)
     ev = tok["edge_valid"] != 0
     assert np.array_equal(logits.view(np.uint32), tl.view(np.uint32)), f"{tag}: {int((logits.view(np.uint32) != tl.view(np.uint32)).sum())} of {int(ev.sum())} logits differ from the host twin"
     assert not scores[~ev].any() and not logits[~ev].any(), f"{tag}: masked entries"
@@ -138,7 +125,7 @@ def test_tanhf_over_its_range():
         if t % 6 == 0:
             tok = env.tokens("pair", 32, 16)
             scores, logits = env.pair_scores(want_logits=True)
-            _, tl = twin_batch(w, tok)
+            _, tl = twin.forward_batch(twin.PAIR, w, tok)
             ev = tok["edge_valid"] != 0
             assert np.array_equal(logits.view(np.uint32), tl.view(np.uint32))
             want = np.tanh(logits.astype(np.float64)) * np.float64(np.float32(w["score_clamp"]))
@@ -219,6 +206,46 @@ def assert_same(a, b, rows, tag):
         assert np.array_equal(np.asarray(a[k])[rows], np.asarray(b[k])[rows]), f"{tag}: {k}"
 
 
+def stepwise(env, seeds, steps, plan):
+    """`plan(env)` then step_staged, `steps` times -> (full state, which envs' episodes ended before the last step, what those held when they ended)"""
+    n = len(seeds)
+    env.reset(seeds)
+    early = np.zeros(n, bool)
+    at_end = {}  # env -> (metrics row, SCALARS row, ERROR) when its episode ended before the last step
+    for t in range(steps):
+        plan(env)
+        env.step_staged()
+        if t < steps - 1:
+            _, term, trunc = env.step_result()
+            new = ((term != 0) | (trunc != 0)) & ~early
+            if new.any():
+                m, sc, er = metrics_of(env), env.get("SCALARS"), env.get("ERROR")
+                for i in np.nonzero(new)[0]:
+                    at_end[int(i)] = (m[i].copy(), sc[i].copy(), int(er[i]))
+                early |= new
+    return full_state(env), early, at_end
+
+
+def compare_paths(case, A, path_b, path_c):
+    """fused state A against the two stepwise paths (each what `stepwise` returned), bit for bit -> (envs compared in full at the last step, envs
+    compared at their earlier end).  An env that flagged a capacity error holds no result and is left out, in every path alike."""
+    (B, early, endB), (Cc, early_c, endC) = path_b, path_c
+    assert np.array_equal(early, early_c) and np.array_equal(B["ERROR"], Cc["ERROR"])
+    ok = (A["ERROR"] == 0) & (B["ERROR"] == 0)
+    assert np.array_equal(A["ERROR"][~early] != 0, B["ERROR"][~early] != 0)
+    assert_same(B, Cc, ok, f"{case} stepwise vs scored chain")
+    assert_same(A, B, ok & ~early, f"{case} fused vs stepwise")
+    n_early = 0
+    for i in np.nonzero(early)[0]:
+        mb, sb, eb = endB[int(i)]
+        mc, scc, ec = endC[int(i)]
+        assert eb == ec and np.array_equal(mb, mc) and np.array_equal(sb, scc), f"{case} env {i}: stepwise vs scored chain at the episode's end"
+        if eb == 0 and A["ERROR"][i] == 0:
+            assert np.array_equal(A["metrics"][i], mb) and np.array_equal(A["SCALARS"][i], sb), f"{case} env {i}: fused vs stepwise at the episode's end"
+            n_early += 1
+    return int((ok & ~early).sum()), n_early
+
+
 @pytest.mark.parametrize("interval,use_vis,wname", [(15, True, "init2"), (20, False, "init2_raw"), (20, True, "il3"), (15, False, "init2_raw")])
 @pytest.mark.parametrize("case,tile", TILE_CASES)
 def test_fused_equals_stepwise_equals_scored_chain(case, tile, interval, use_vis, wname):
@@ -238,25 +265,8 @@ def test_fused_equals_stepwise_equals_scored_chain(case, tile, interval, use_vis
     A = full_state(fused)
     assert np.array_equal(A["metrics"], rm)
 
-    def stepwise(env, plan):
-        env.reset(seeds)
-        early = np.zeros(n, bool)
-        at_end = {}  # env -> (metrics row, SCALARS row, ERROR) when its episode ended before the last step
-        for t in range(steps):
-            plan(env)
-            env.step_staged()
-            if t < steps - 1:
-                _, term, trunc = env.step_result()
-                new = ((term != 0) | (trunc != 0)) & ~early
-                if new.any():
-                    m, sc, er = metrics_of(env), env.get("SCALARS"), env.get("ERROR")
-                    for i in np.nonzero(new)[0]:
-                        at_end[int(i)] = (m[i].copy(), sc[i].copy(), int(er[i]))
-                    early |= new
-        return full_state(env), early, at_end
-
     step, _ = _policy_env(case, n, wname)
-    B, early, endB = stepwise(step, lambda e: e.allocate(interval, use_vis, fetch=False))
+    path_b = stepwise(step, seeds, steps, lambda e: e.allocate(interval, use_vis, fetch=False))
     chain, _ = _policy_env(case, n, wname)
     chain.set_allocator("hungarian")  # the scores come through the stand-alone kernel: no allocator mode involved
     sc = torch.empty((n, 16, 32), dtype=torch.float32, device=torch.device("cuda", chain.device_index))
@@ -264,22 +274,9 @@ def test_fused_equals_stepwise_equals_scored_chain(case, tile, interval, use_vis
     def plan_chain(e):
         e.pair_scores(out={"scores": sc})
         e.allocate_scored(_kind(w), 32, 16, edge_scores=sc, gate="trainer", replan_interval=interval, use_visibility=use_vis, edge_valid_only=True, out={})
-    Cc, early_c, endC = stepwise(chain, plan_chain)
-    assert np.array_equal(early, early_c) and np.array_equal(B["ERROR"], Cc["ERROR"])
-    ok = (A["ERROR"] == 0) & (B["ERROR"] == 0)
-    assert np.array_equal(A["ERROR"][~early] != 0, B["ERROR"][~early] != 0)
-    assert_same(B, Cc, ok, f"{case} stepwise vs scored chain")
-    assert_same(A, B, ok & ~early, f"{case} fused vs stepwise")
-    n_early = 0
-    for i in np.nonzero(early)[0]:
-        mb, sb, eb = endB[int(i)]
-        mc, scc, ec = endC[int(i)]
-        assert eb == ec and np.array_equal(mb, mc) and np.array_equal(sb, scc), f"{case} env {i}: stepwise vs scored chain at the episode's end"
-        if eb == 0 and A["ERROR"][i] == 0:
-            assert np.array_equal(A["metrics"][i], mb) and np.array_equal(A["SCALARS"][i], sb), f"{case} env {i}: fused vs stepwise at the episode's end"
-            n_early += 1
-    compared = int((ok & ~early).sum()) + n_early
-    print(f"{case} {wname} interval {interval} vis {use_vis}: {n} envs, {int((ok & ~early).sum())} compared in full at step {steps}, {n_early} at their earlier end, "
+    full, n_early = compare_paths(case, A, path_b, stepwise(chain, seeds, steps, plan_chain))
+    compared = full + n_early
+    print(f"{case} {wname} interval {interval} vis {use_vis}: {n} envs, {full} compared in full at step {steps}, {n_early} at their earlier end, "
           f"{n - compared} outgrew the tile")
     assert compared >= 256, f"{compared} of {n} envs compared"
     assert A["SCALARS"][:, 23].max() >= 5  # plans were made
@@ -396,7 +393,7 @@ def test_fused_episodes_vs_reference(key, paths):
         for t in range(150):
             tok = env.tokens(_kind(w), 32, 16)
             got = env.pair_scores()[0]
-            s64, _ = twin.forward64(w, tok["agent_feats"][0], tok["task_feats"][0], tok["edge_valid"][0])
+            s64, _ = twin.forward64(twin.PAIR, w, {k: v[0] for k, v in tok.items()})
             ev = tok["edge_valid"][0] != 0
             if ev.any():
                 worst = max(worst, float(np.abs(got.astype(np.float64) - s64)[ev].max()))

@@ -1,5 +1,5 @@
 """No-GPU checks of the learned MLP-Coalition policy: the fixtures recorded from the reference (tools/gen_golden_mlp_coalition.py) are
-consistent and meet the condition the GPU episode test rests on, the host twin of the device's arithmetic (tests/coalition_mlp_py.py)
+consistent and meet the condition the GPU episode test rests on, the host twin of the device's arithmetic (tests/policy_mlp_py.py)
 agrees with the reference's float64 evaluation within the bound the GPU test uses, the parser accepts and refuses what the issue lists,
 and the frozen C ABI / Python surface carries the new kind without a new symbol or allocator number."""
 import glob
@@ -9,11 +9,9 @@ import re
 import numpy as np
 import pytest
 
-import coalition_mlp_py as twin
-import context_pair_mlp_py
-import pair_mlp_py
+import policy_mlp_py as twin
 from muavta_amd import native
-from muavta_amd.batched import BatchedMultiUAVEnv
+from muavta_amd.batched import POLICY_KINDS, BatchedMultiUAVEnv
 from muavta_amd.native import MuavtaError
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,12 +22,7 @@ KEYS = twin.KEYS
 
 
 def _weights(name):
-    z = np.load(os.path.join(GOLDEN, f"mlpcoal_weights_{name}.npz"))
-    if "base" in z.files:  # layer 3 only, over another set
-        w = _weights(str(z["base"]))
-        w["w2"], w["b2"] = np.ascontiguousarray(z["w2"], np.float32), np.ascontiguousarray(z["b2"], np.float32)
-        return w
-    return twin.load_weights(os.path.join(GOLDEN, f"mlpcoal_weights_{name}.npz"))
+    return twin.load_weights(twin.COALITION, name)
 
 
 def _valid(g):
@@ -88,10 +81,10 @@ def test_twin_vs_reference_float64(path):
     ok = _valid(g)
     worst = 0.0
     for k in range(0, len(g["step"]), 8):
-        s, lg = twin.forward32(w, g["af"][k], g["amask"][k], g["tf"][k], g["tmask"][k], g["ev"][k])
+        s, lg = twin.forward(twin.COALITION, w, twin.trace_tokens(g, k))
         assert not s[~ok[k]].any() and not lg[~ok[k]].any()
         worst = max(worst, float(np.abs(s.astype(np.float64) - g["scores64"][k])[ok[k]].max()) if ok[k].any() else 0.0)
-        s64, _ = twin.forward64(w, g["af"][k], g["amask"][k], g["tf"][k], g["tmask"][k], g["ev"][k])
+        s64, _ = twin.forward64(twin.COALITION, w, twin.trace_tokens(g, k))
         # (the generator wrote scores64 with this very function: the line only catches drift between the twin's file and the fixtures.  The
         # independent link to the reference is torch's own float32 `scores` in the fixture, within d_ref < 1e-6 of scores64 — test_trace_is_consistent.)
         assert np.array_equal(s64, g["scores64"][k])
@@ -107,13 +100,13 @@ def test_twin_is_a_pure_function_of_the_pair_and_clips_at_20():
     am, tm = np.zeros(16, np.uint8), np.zeros(48, np.uint8)
     af[5], af[9], tf[7], tf[40] = af[2], af[2], tf[3], tf[3]       # duplicated rows
     ev = np.zeros((16, 48), np.float32); ev[[2, 5, 9]] = 1; ev[:, [3, 7, 40]] = 1
-    s, lg = twin.forward32(w, af, am, tf, tm, ev)
+    s, lg = twin.forward(twin.COALITION, w, {"agent_feats": af, "agent_mask": am, "task_feats": tf, "task_mask": tm, "edge_valid": ev})
     u = lg.view(np.uint32)
     assert np.array_equal(u[5], u[2]) and np.array_equal(u[9], u[2]) and np.array_equal(u[:, 7], u[:, 3]) and np.array_equal(u[:, 40], u[:, 3])
     # a plan of the 24-agent escort case with the wide set: both clip sides, each one value — sigmoid at +-20 itself
     g = np.load(os.path.join(GOLDEN, "mlpcoal_trace_WPS_escort24_s0.npz"))
     kk = int(np.nonzero(g["step"] == 40)[0][0])   # a plan whose logits straddle both bounds
-    sw, lw = twin.forward32(w, g["af"][kk], g["amask"][kk], g["tf"][kk], g["tmask"][kk], g["ev"][kk])
+    sw, lw = twin.forward(twin.COALITION, w, twin.trace_tokens(g, kk))
     on = g["ev"][kk] != 0
     assert (lw[on] > 20).any() and (lw[on] < -20).any() and (np.abs(lw[on]) < 20).any()
     assert np.all(sw[on & (lw > 20)] == twin.sigmoid32(np.float32(20))) and np.all(sw[on & (lw < -20)] == twin.sigmoid32(np.float32(-20)))
@@ -121,7 +114,7 @@ def test_twin_is_a_pure_function_of_the_pair_and_clips_at_20():
     assert np.abs(sw.astype(np.float64) - twin.sigmoid64(lw))[on].max() <= 4 * 2.0 ** -24
     # a pad row masks its pairs whatever edge_valid says
     am[5] = 1
-    s2, lg2 = twin.forward32(w, af, am, tf, tm, ev)
+    s2, lg2 = twin.forward(twin.COALITION, w, {"agent_feats": af, "agent_mask": am, "task_feats": tf, "task_mask": tm, "edge_valid": ev})
     assert not s2[5].any() and not lg2[5].any() and np.array_equal(s2[2], s[2])
 
 
@@ -181,7 +174,7 @@ def test_parser_reads_a_saved_checkpoint_and_refuses_what_the_device_cannot_run(
     with pytest.raises(ValueError, match="hidden = 128"):
         BatchedMultiUAVEnv.parse_pair_policy(dict(ck, state_dict=narrow))
     with pytest.raises(ValueError, match="pair_mlp.0.weight"):   # a 25-column net under an AttentionEscort checkpoint
-        BatchedMultiUAVEnv.parse_pair_policy(dict(ck, state_dict=pair_mlp_py.as_state_dict(pair_mlp_py.load_weights(os.path.join(GOLDEN, "mlppair_weights_init2.npz")))))
+        BatchedMultiUAVEnv.parse_pair_policy(dict(ck, state_dict=twin.as_state_dict(twin.load_weights(twin.PAIR, "init2"))))
     bad = twin.as_state_dict(w)
     bad["pair_mlp.2.weight"] = z(256, 128)
     with pytest.raises(ValueError, match="pair_mlp.2.weight"):
@@ -189,11 +182,10 @@ def test_parser_reads_a_saved_checkpoint_and_refuses_what_the_device_cannot_run(
 
 
 def test_every_old_refusal_of_the_parser_still_holds():
-    w128 = pair_mlp_py.load_weights(os.path.join(GOLDEN, "mlppair_weights_init2.npz"))
-    w192 = context_pair_mlp_py.load_weights(os.path.join(GOLDEN, "mlpctx_weights_init2.npz"))
-    assert BatchedMultiUAVEnv.parse_pair_policy(pair_mlp_py.as_state_dict(w128))["kind"] == "pair"
-    assert BatchedMultiUAVEnv.parse_pair_policy(context_pair_mlp_py.as_state_dict(w192))["kind"] == "context"
-    ck = {"state_dict": {k: v for k, v in context_pair_mlp_py.as_state_dict(w192).items() if k.startswith("pair_mlp")}, "use_attention": False,
+    w128, w192 = twin.load_weights(twin.PAIR, "init2"), twin.load_weights(twin.CONTEXT, "init2")
+    assert BatchedMultiUAVEnv.parse_pair_policy(twin.as_state_dict(w128))["kind"] == "pair"
+    assert BatchedMultiUAVEnv.parse_pair_policy(twin.as_state_dict(w192))["kind"] == "context"
+    ck = {"state_dict": {k: v for k, v in twin.as_state_dict(w192).items() if k.startswith("pair_mlp")}, "use_attention": False,
           "max_tasks": 32, "max_agents": 16, "score_clamp": 0.35, "raw_features": False, "kind": "MLPContextPair"}
     with pytest.raises(ValueError, match="Att-ContextPair"):
         BatchedMultiUAVEnv.parse_pair_policy(dict(ck, use_attention=True, kind="AttContextPair"))
@@ -202,7 +194,7 @@ def test_every_old_refusal_of_the_parser_still_holds():
     with pytest.raises(ValueError, match="use_attention"):
         BatchedMultiUAVEnv.parse_pair_policy(dict(ck, use_attention=True))
     with pytest.raises(ValueError, match="raw_features"):
-        BatchedMultiUAVEnv.parse_pair_policy(dict(context_pair_mlp_py.as_state_dict(w192), raw_features=True))
+        BatchedMultiUAVEnv.parse_pair_policy(dict(twin.as_state_dict(w192), raw_features=True))
     with pytest.raises(ValueError, match="pair_mlp.0.weight"):
         BatchedMultiUAVEnv.parse_pair_policy(dict(ck, kind="PairCostHybrid"))
     with pytest.raises(ValueError, match="pair_mlp.0.weight"):   # a 38-column net under a pair / context checkpoint is not a coalition
@@ -232,9 +224,12 @@ def test_the_frozen_surface_carries_the_new_kind():
     assert "MLP-Coalition [N, 16, 48]" in header and "score_clamp is IGNORED" in header
 
 
-def test_set_allocator_coalition_name_needs_a_coalition_policy():
+def test_set_allocator_kind_names_need_a_policy_of_their_kind():
     env = BatchedMultiUAVEnv.__new__(BatchedMultiUAVEnv)   # no handle: the name is refused before the library is called
-    for rec in (None, {"kind": "pair"}, {"kind": "context"}):
-        env._pair_policy = rec
-        with pytest.raises(MuavtaError, match="MLP-Coalition"):
-            env.set_allocator("mlp_coalition")
+    needs = {k.alias: k for k in POLICY_KINDS.values() if k.alias}
+    assert {name: k.label for name, k in needs.items()} == {"mlp_context_pair": "MLP-ContextPair", "mlp_coalition": "MLP-Coalition"}
+    for name, need in needs.items():
+        for rec in [None] + [{"kind": other} for other in POLICY_KINDS if other != need.name]:
+            env._pair_policy = rec
+            with pytest.raises(MuavtaError, match=need.label):
+                env.set_allocator(name)

@@ -1,6 +1,6 @@
 """No-GPU checks of the learned MLP-ContextPair policy: the fixtures recorded from the reference (tools/gen_golden_mlp_context_pair.py)
 are consistent and meet the condition the GPU episode test rests on, the host twin of the device's arithmetic
-(tests/context_pair_mlp_py.py) agrees with the reference's float64 evaluation within the bound the GPU test uses, the column
+(tests/policy_mlp_py.py) agrees with the reference's float64 evaluation within the bound the GPU test uses, the column
 permutation and the pools are what the contract says, and the C ABI / Python surface carries the new entry point."""
 import ctypes as C
 import glob
@@ -11,11 +11,9 @@ import subprocess
 import numpy as np
 import pytest
 
-import context_pair_mlp_py as twin
-import pair_mlp_py
+import policy_mlp_py as twin
 from muavta_amd import native
 from muavta_amd.batched import BatchedMultiUAVEnv
-from muavta_amd.native import MuavtaError
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -26,14 +24,14 @@ KEYS = ("w0", "b0", "w1", "b1", "w2", "b2")
 
 
 def _weights(name):
-    return twin.load_weights(os.path.join(GOLDEN, f"mlpctx_weights_{name}.npz"))
+    return twin.load_weights(twin.CONTEXT, name)
 
 
 # 1. fixtures
 def test_fixture_sets_are_complete_and_meet_the_episode_condition():
     assert {os.path.basename(p)[len("mlpctx_weights_"):-4] for p in WEIGHTS} == {"init2", "init2_raw", "il3"}
     assert len(TRACES) == 7 and len(METRICS) == 5
-    sets = {os.path.basename(p)[len("mlpctx_weights_"):-4]: twin.load_weights(p) for p in WEIGHTS}
+    sets = {name: _weights(name) for name in twin.weight_sets(twin.CONTEXT)}
     for name, w in sets.items():
         assert w["raw_features"] == (name == "init2_raw")
         assert w["w0"].shape == (192, 41 if w["raw_features"] else 58) and w["w1"].shape == (192, 192) and w["w2"].shape == (1, 192)
@@ -82,11 +80,11 @@ def test_twin_vs_reference_float64(path):
     D = float(g["d_ref"])
     worst = 0.0
     for k in range(0, len(g["step"]), 3):
-        s, lg = twin.forward(w, g["af"][k], g["amask"][k], g["tf"][k], g["tmask"][k], g["ctx"][k], g["ev"][k])
+        s, lg = twin.forward(twin.CONTEXT, w, twin.trace_tokens(g, k))
         ev = g["ev"][k] != 0
         assert not s[~ev].any() and not lg[~ev].any()
         worst = max(worst, float(np.abs(s.astype(np.float64) - g["scores64"][k])[ev].max()) if ev.any() else 0.0)
-        s64, _ = twin.forward64(w, g["af"][k], g["amask"][k], g["tf"][k], g["tmask"][k], g["ctx"][k], g["ev"][k])
+        s64, _ = twin.forward64(twin.CONTEXT, w, twin.trace_tokens(g, k))
         # (the generator wrote scores64 with this very function: the line only catches drift between the twin's file and the fixtures.  The
         # independent link to the reference is torch's own float32 `scores` in the fixture, within d_ref < 1e-6 of scores64 — test_trace_is_consistent.)
         assert np.array_equal(s64, g["scores64"][k])
@@ -110,7 +108,7 @@ def test_column_permutation(raw):
     # through the twin: an identity layer 1 in state_dict order applied to a device-order row gives the row back in state_dict order
     w = {"w0": np.eye(192, K, dtype=np.float32), "b0": np.zeros(192, np.float32)}
     x = (np.arange(K, dtype=np.float32) + 1)[None, :]            # device-order row: position k holds k + 1
-    h = pair_mlp_py.linear(np.ascontiguousarray(w["w0"][:, perm]), w["b0"], x)[0, :K]
+    h = twin.linear(np.ascontiguousarray(w["w0"][:, perm]), w["b0"], x)[0, :K]
     assert np.array_equal(h, (np.argsort(perm) + 1).astype(np.float32))
 
 
@@ -155,7 +153,7 @@ def test_twin_is_a_pure_function_of_the_pair_within_an_env():
     am, tm = np.zeros(16, np.uint8), np.zeros(32, np.uint8)
     af[5], af[9], tf[7], tf[30] = af[2], af[2], tf[3], tf[3]       # duplicated rows
     ev = np.zeros((16, 32), np.float32); ev[[2, 5, 9]] = 1; ev[:, [3, 7, 30]] = 1
-    _, lg = twin.forward(w, af, am, tf, tm, g["ctx"][k], ev)
+    _, lg = twin.forward(twin.CONTEXT, w, {"agent_feats": af, "agent_mask": am, "task_feats": tf, "task_mask": tm, "context": g["ctx"][k], "edge_valid": ev})
     lg = lg.view(np.uint32)
     assert np.array_equal(lg[5], lg[2]) and np.array_equal(lg[9], lg[2]) and np.array_equal(lg[:, 7], lg[:, 3]) and np.array_equal(lg[:, 30], lg[:, 3])
 
@@ -163,7 +161,7 @@ def test_twin_is_a_pure_function_of_the_pair_within_an_env():
 # 3. the parser
 @pytest.mark.parametrize("path", WEIGHTS, ids=lambda p: os.path.basename(p)[:-4])
 def test_weights_load_through_the_parser(path):
-    w = twin.load_weights(path)
+    w = _weights(os.path.basename(path)[len("mlpctx_weights_"):-4])
     pol = BatchedMultiUAVEnv.parse_pair_policy(twin.as_state_dict(w))
     assert pol["kind"] == "context" and pol["hidden"] == 192 and pol["raw_features"] == w["raw_features"] and pol["score_clamp"] == w["score_clamp"]
     for k in KEYS:
@@ -199,8 +197,8 @@ def test_parser_reads_a_saved_checkpoint_and_refuses_what_the_device_cannot_run(
         net, use_attention, raw_features, score_clamp, kind = Net(), False, False, 0.35, "MLPContextPair"
     assert BatchedMultiUAVEnv.parse_pair_policy(Hybrid())["kind"] == "context"
     # an MLP-Pair still parses as before
-    w128 = pair_mlp_py.load_weights(os.path.join(GOLDEN, "mlppair_weights_init2.npz"))
-    pol = BatchedMultiUAVEnv.parse_pair_policy(pair_mlp_py.as_state_dict(w128))
+    w128 = twin.load_weights(twin.PAIR, "init2")
+    pol = BatchedMultiUAVEnv.parse_pair_policy(twin.as_state_dict(w128))
     assert pol["kind"] == "pair" and pol["hidden"] == 128
     # refusals
     with pytest.raises(ValueError, match="Att-ContextPair"):
@@ -240,16 +238,6 @@ def test_new_symbol_is_declared_exported_and_bound():
     assert re.search(r"MUAVTA_ALLOC_MLP_PAIR\s*=\s*6\s*\}", text)
     assert BatchedMultiUAVEnv.ALLOCATORS["mlp_context_pair"] == 6 == BatchedMultiUAVEnv.ALLOCATORS["mlp_pair"]
     assert max(BatchedMultiUAVEnv.ALLOCATORS.values()) == 6 and 7 not in BatchedMultiUAVEnv.ALLOCATORS.values()
-
-
-def test_set_allocator_context_name_needs_a_context_policy():
-    env = BatchedMultiUAVEnv.__new__(BatchedMultiUAVEnv)   # no handle: the name is refused before the library is called
-    env._pair_policy = None
-    with pytest.raises(MuavtaError, match="MLP-ContextPair"):
-        env.set_allocator("mlp_context_pair")
-    env._pair_policy = {"kind": "pair"}
-    with pytest.raises(MuavtaError, match="MLP-ContextPair"):
-        env.set_allocator("mlp_context_pair")
 
 
 def test_context_pair_mlp_struct_matches_the_header(tmp_path):

@@ -1,5 +1,5 @@
 """No-GPU checks of the learned MLP-Pair mode: the fixtures recorded from the reference (tools/gen_golden_mlp_pair.py) are consistent,
-the host twin of the device's arithmetic (tests/pair_mlp_py.py) agrees with the reference's float64 evaluation within the bound the GPU
+the host twin of the device's arithmetic (tests/policy_mlp_py.py) agrees with the reference's float64 evaluation within the bound the GPU
 test uses, and the C ABI / Python surface carries the new entry points."""
 import ctypes as C
 import glob
@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import pair_mlp_py as twin
+import policy_mlp_py as twin
 from muavta_amd import native
 from muavta_amd.batched import BatchedMultiUAVEnv
 
@@ -22,7 +22,7 @@ METRICS = sorted(glob.glob(os.path.join(GOLDEN, "mlppair_metrics_*.npz")))
 
 
 def _weights(name):
-    return twin.load_weights(os.path.join(GOLDEN, f"mlppair_weights_{name}.npz"))
+    return twin.load_weights(twin.PAIR, name)
 
 
 def d_ref(g):
@@ -34,7 +34,7 @@ def d_ref(g):
 # 1. fixture integrity
 def test_fixture_sets_are_complete():
     assert len(WEIGHTS) >= 3 and len(TRACES) >= 6 and len(METRICS) >= 4
-    sets = {os.path.basename(p)[len("mlppair_weights_"):-4]: twin.load_weights(p) for p in WEIGHTS}
+    sets = {name: _weights(name) for name in twin.weight_sets(twin.PAIR)}
     assert any(w["raw_features"] for w in sets.values()) and any(not w["raw_features"] for w in sets.values())
     for p in TRACES + METRICS:
         assert str(np.load(p)["weights"]) in sets, p
@@ -82,7 +82,7 @@ def test_trace_is_consistent(path):
 
 @pytest.mark.parametrize("path", WEIGHTS, ids=lambda p: os.path.basename(p)[:-4])
 def test_weights_load_through_the_parser(path):
-    w = twin.load_weights(path)
+    w = _weights(os.path.basename(path)[len("mlppair_weights_"):-4])
     pol = BatchedMultiUAVEnv.parse_pair_policy(twin.as_state_dict(w))
     assert pol["hidden"] == 128 and pol["raw_features"] == w["raw_features"] and pol["score_clamp"] == w["score_clamp"]
     for k in ("w0", "b0", "w1", "b1", "w2", "b2"):
@@ -154,11 +154,11 @@ def test_twin_vs_reference_float64(path):
     assert 0 < D < 1e-6
     worst = 0.0
     for k in range(len(g["step"])):
-        s, lg = twin.forward(w, g["af"][k], g["tf"][k], g["ev"][k])
+        s, lg = twin.forward(twin.PAIR, w, twin.trace_tokens(g, k))
         ev = g["ev"][k] != 0
         assert not s[~ev].any() and not lg[~ev].any()
         worst = max(worst, float(np.abs(s.astype(np.float64) - g["scores64"][k])[ev].max()) if ev.any() else 0.0)
-        s64, _ = twin.forward64(w, g["af"][k], g["tf"][k], g["ev"][k])
+        s64, _ = twin.forward64(twin.PAIR, w, twin.trace_tokens(g, k))
         assert np.array_equal(s64, g["scores64"][k])
     print(f"{os.path.basename(path)}: D_ref {D:.3e}, twin {worst:.3e}, ratio {worst / D:.2f}")
     assert worst <= 4 * D
@@ -171,13 +171,13 @@ def test_twin_is_a_pure_function_of_the_pair():
     af, tf = g["af"][k].copy(), g["tf"][k].copy()
     ev = np.ones((16, 32), np.float32)
     af[5], af[9], tf[7], tf[30] = af[2], af[2], tf[3], tf[3]       # duplicated rows
-    _, lg = twin.forward(w, af, tf, ev)
+    _, lg = twin.forward(twin.PAIR, w, {"agent_feats": af, "task_feats": tf, "edge_valid": ev})
     assert np.array_equal(lg[5].view(np.uint32), lg[2].view(np.uint32)) and np.array_equal(lg[9].view(np.uint32), lg[2].view(np.uint32))
     assert np.array_equal(lg[:, 7].view(np.uint32), lg[:, 3].view(np.uint32)) and np.array_equal(lg[:, 30].view(np.uint32), lg[:, 3].view(np.uint32))
     rng = np.random.default_rng(1)
     pa, pt = rng.permutation(16), rng.permutation(32)                 # permuted rows / columns, and a sparser mask
     ev2 = (rng.uniform(size=(16, 32)) < 0.3).astype(np.float32)
-    _, lg2 = twin.forward(w, af[pa], tf[pt], ev2)
+    _, lg2 = twin.forward(twin.PAIR, w, {"agent_feats": af[pa], "task_feats": tf[pt], "edge_valid": ev2})
     want = np.where(ev2 != 0, lg[pa][:, pt], np.float32(0))
     assert np.array_equal(lg2.view(np.uint32), want.view(np.uint32))
 

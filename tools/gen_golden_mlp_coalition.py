@@ -14,7 +14,7 @@ tools/gen_golden_mlp_context_pair.py.  Output under tests/golden/:
       wide    layer 3 only (w2, b2; the rest is init2's, `base`): init2's layer 3 x WIDE_SCALE with the bias moved so that the logits of
               init2's WPS_escort trace are centred — logits beyond +-20 on both sides and inside +-1 (asserted below)
   mlpcoal_trace_<tag>_s<seed>.npz      one episode, per plan: step, tf / af / tid / aid / tmask / amask / ev (the tokens), the policy's float32
-                                       scores and logits (AttentionEscort.act, explore=False), scores64 (tests/coalition_mlp_py.forward64 on
+                                       scores and logits (AttentionEscort.act, explore=False), scores64 (tests/policy_mlp_py.forward64 on
                                        the same float32 tokens), selected (_selected_mask), commit_until (every agent, after the plan), pairs,
                                        actions; per step replanned; the 30 metrics and hung_force.n_replans; d_ref = max |scores - scores64|
                                        over the valid pairs
@@ -45,7 +45,7 @@ import TaskAllocation.OptimizationBased.HungarianAllocator as HA  # noqa: E402
 from experiments.paper_eval import _events  # noqa: E402
 from TaskAllocation.Hybrid.AttentionEscort import AttentionEscort  # noqa: E402
 
-import coalition_mlp_py as twin  # noqa: E402
+import policy_mlp_py as twin  # noqa: E402
 
 KEYS = twin.KEYS
 SD = ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias"), (4, "weight"), (4, "bias"))
@@ -64,7 +64,7 @@ def seed_all(s):
 
 
 def new_policy():
-    p = AttentionEscort(use_attention=False, max_tasks=twin.MT, max_agents=twin.MA, device="cpu")
+    p = AttentionEscort(use_attention=False, max_tasks=twin.COALITION.max_tasks, max_agents=twin.COALITION.max_agents, device="cpu")
     p.eps = 0.0
     return p
 
@@ -136,13 +136,13 @@ def run_episode(case, seed, policy, w, use64, record):
             scores, noise, logits = policy.act(tok, explore=False)
             s64 = None
             if use64 or record:
-                s64, _ = twin.forward64(w, tok["agent_feats"], tok["agent_mask"], tok["task_feats"], tok["task_mask"], tok["edge_valid"])
+                s64, _ = twin.forward64(twin.COALITION, w, tok)
             result = policy._plan_from_scores(env, hung_force, tok, s64.astype(np.float32) if use64 else scores, events=events, force=True)
             actions = E._apply_assign(env, result)
             if record:
-                tid, aid = _ids(tok, twin.MT, twin.MA)
+                tid, aid = _ids(tok, twin.COALITION.max_tasks, twin.COALITION.max_agents)
                 commit = np.array([int(getattr(a, "commit_until", 0) or 0) for a in sorted(env.agents_obj, key=lambda u: u.id)], dtype=np.int64)
-                ok = twin.valid_pairs(tok["agent_mask"], tok["task_mask"], tok["edge_valid"])
+                ok = twin.cells(twin.COALITION, tok)
                 for k, v in zip(rec, (env.time_steps, tok["task_feats"], tok["agent_feats"], tid, aid, np.asarray(tok["task_mask"], np.uint8),
                                          np.asarray(tok["agent_mask"], np.uint8), tok["edge_valid"], scores, logits * ok, s64, policy._selected_mask(tok, result), commit)):
                     rec[k].append(np.asarray(v).copy())
@@ -193,7 +193,7 @@ def gen_wide():
     lo = hi = 0.0
     small = False
     for k in range(len(tr["step"])):
-        _, l32 = twin.forward32(wide, tr["af"][k], tr["amask"][k], tr["tf"][k], tr["tmask"][k], tr["ev"][k])
+        _, l32 = twin.forward(twin.COALITION, wide, twin.trace_tokens(tr, k))
         v = l32[ok[k]]
         if len(v):
             lo, hi, small = min(lo, float(v.min())), max(hi, float(v.max())), small or bool((np.abs(v) < 1).any())

@@ -13,7 +13,7 @@ The sibling of tools/gen_golden_mlp_pair.py.  Output under tests/golden/:
       init2_raw  the same with raw_features=True (seed 8)
       il3        3 imitation episodes of train_pair_cost.run_il_episode on WPS_attn from the default init (seed 9)
   mlpctx_trace_<tag>_s<seed>.npz       one episode, per plan: step, tf / af / tid / aid / tmask / amask / ev (the tokens), ctx (the context
-                                       summary), torch's float32 scores and logits, scores64 (tests/context_pair_mlp_py.forward64: the
+                                       summary), torch's float32 scores and logits, scores64 (tests/policy_mlp_py.forward64: the
                                        same net, pooling included, on the same float32 tokens and context in float64), selected
                                        (_selected_mask), pairs, actions; per step replanned; the 30 metrics, hung.n_replans and
                                        policy.n_replans; d_ref = max |scores - scores64| over the valid pairs
@@ -45,7 +45,7 @@ import TaskAllocation.OptimizationBased.HungarianAllocator as HA  # noqa: E402
 from experiments.paper_eval import _events  # noqa: E402
 from TaskAllocation.Hybrid.ContextPairHybrid import ContextPairHybrid  # noqa: E402
 
-import context_pair_mlp_py as twin  # noqa: E402
+import policy_mlp_py as twin  # noqa: E402
 
 KEYS = ("w0", "b0", "w1", "b1", "w2", "b2")
 # tag suffix, weight set, interval, loop
@@ -104,7 +104,7 @@ def save_weights(name, w):
 
 
 def load_policy(name):
-    w = twin.load_weights(os.path.join(OUT, f"mlpctx_weights_{name}.npz"))
+    w = twin.load_weights(twin.CONTEXT, name)
     p = new_policy(w["raw_features"])
     p.score_clamp = w["score_clamp"]
     sd = p.net.state_dict()
@@ -134,7 +134,7 @@ def run_episode(case, seed, policy, w, interval, use64, record):
             s_in = None
             if use64 or record:
                 tok0 = policy.build_tokens(env)
-                s64, _ = twin.forward64(w, tok0["agent_feats"], tok0["agent_mask"], tok0["task_feats"], tok0["task_mask"], tok0["context"], tok0["edge_valid"])
+                s64, _ = twin.forward64(twin.CONTEXT, w, tok0)
                 if use64:
                     s_in = s64.astype(np.float32)
             result, tok, scores, noise, logits, selected = policy.plan(env, hung, events=events, explore=False, force=True, scores=s_in)

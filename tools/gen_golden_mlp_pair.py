@@ -13,7 +13,7 @@ tools/gen_golden.py builds it.  Output under tests/golden/:
       init2_raw  the same with raw_features=True (seed 8)
       il3        3 imitation episodes of train_pair_cost.run_il_episode on WPS_hard from the default init (seed 9)
   mlppair_trace_<tag>_s<seed>.npz      one episode, per plan: step, tf / af / tid / aid / ev (the tokens), torch's float32 scores and
-                                       logits, scores64 (tests/pair_mlp_py.forward64: the same net on the same tokens in float64),
+                                       logits, scores64 (tests/policy_mlp_py.forward64: the same net on the same tokens in float64),
                                        selected (_selected_mask), pairs, actions; per step replanned; the 30 metrics, hung.n_replans
                                        (the HungarianAllocator's counter) and policy.n_replans (non-empty results only)
   mlppair_metrics_<tag>.npz            per seed: metrics32 / n_replans32 with the policy's own float32 scores, metrics64 / n_replans64
@@ -44,7 +44,7 @@ import TaskAllocation.OptimizationBased.HungarianAllocator as HA  # noqa: E402
 from experiments.paper_eval import _events  # noqa: E402
 from TaskAllocation.Hybrid.PairCostHybrid import PairCostHybrid  # noqa: E402
 
-import pair_mlp_py as twin  # noqa: E402
+import policy_mlp_py as twin  # noqa: E402
 
 KEYS = ("w0", "b0", "w1", "b1", "w2", "b2")
 # tag suffix, weight set, interval, loop
@@ -103,7 +103,7 @@ def save_weights(name, w):
 
 
 def load_policy(name):
-    w = twin.load_weights(os.path.join(OUT, f"mlppair_weights_{name}.npz"))
+    w = twin.load_weights(twin.PAIR, name)
     p = new_policy(w["raw_features"])
     p.score_clamp = w["score_clamp"]
     sd = p.net.state_dict()
@@ -133,7 +133,7 @@ def run_episode(case, seed, policy, w, interval, use64, record):
             s_in = None
             if use64 or record:
                 tok0 = policy.build_tokens(env)
-                s64, _ = twin.forward64(w, tok0["agent_feats"], tok0["task_feats"], tok0["edge_valid"])
+                s64, _ = twin.forward64(twin.PAIR, w, tok0)
                 if use64:
                     s_in = s64.astype(np.float32)
             result, tok, scores, noise, logits, selected = policy.plan(env, hung, events=events, explore=False, force=True, scores=s_in)
