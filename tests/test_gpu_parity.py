@@ -2316,19 +2316,21 @@ def test_context_vector_vs_reference_and_oracle(path):
             o.step(aa[i][:kk], ai[i][:kk])
 
 
-@pytest.mark.skipif(os.environ.get("MUAVTA_UNVERIFIED_GPU_TESTS") != "1",
-                    reason="written after round 5's GPU minutes were spent and never run on a device: MUAVTA_UNVERIFIED_GPU_TESTS=1 enables it; verify, then drop the guard")
 def test_facade_switch_write_after_reset_recreates_the_handle_on_the_gpu():
     """main.py:130-141 assigns `multiple_tasks_per_agent = True` on the env object right after reset().  The facade re-creates the device handle with the new
     parameter and the episode's seed and swaps it in after comparing the resident state of the two handles (env.py: the property's setter).  Over the HIP
     backend the episode that follows must equal, call by call, the one the same facade gives over the oracle backend (which the CPU suite compares with the
-    reference env: tests/test_facade_cpu.py), and a write after a step must raise."""
+    reference env: tests/test_facade_cpu.py), and a write after a step must raise.
+    The random lists below queue up to 11 tasks on one agent (seed 6, from step 32 on; 10 with seed 5): one more than the 16 x 40 tile's queue holds, so
+    the handle is made on the 24 x 48 tile, whose queue holds 12; the re-created handle keeps the tile.  (The facade itself does not read ERROR after a
+    step: DESIGN.md section 10.)"""
     from oracle_backend import OracleBackend
     from muavta_amd.env import MultiUAVEnv
     from muavta_amd.scenarios import CASE_SPECS
 
     flags = {"multiple_tasks_per_agent": False}
-    hip, cpu = MultiUAVEnv(CASE_SPECS["static_strike"], flags=dict(flags)), MultiUAVEnv(CASE_SPECS["static_strike"], flags=dict(flags), backend_factory=OracleBackend)
+    hip = MultiUAVEnv(CASE_SPECS["static_strike"], flags=dict(flags), tile_agents=24, tile_tasks=48, tile_threats=24)
+    cpu = MultiUAVEnv(CASE_SPECS["static_strike"], flags=dict(flags), backend_factory=OracleBackend)
     assert type(hip.backend).__name__ == "BatchedMultiUAVEnv" and hip.multiple_tasks_per_agent is False
     first = hip.backend
     for seed in (5, 6):
@@ -2343,6 +2345,8 @@ def test_facade_switch_write_after_reset_recreates_the_handle_on_the_gpu():
             assert [x.id for x in hip.last_tasks_info] == [x.id for x in cpu.last_tasks_info], (seed, t)
             acts = {a.name: [int(x) for x in rng.integers(1, n_open, size=int(rng.integers(1, 4)))] for a in cpu.get_live_agents()[: 1 + t % 3]} if n_open > 1 and t % 4 == 0 else {}
             r_hip, r_cpu = hip.step({k: list(v) for k, v in acts.items()}), cpu.step({k: list(v) for k, v in acts.items()})
+            assert max(len(a.tasks) for a in cpu.agents_obj) <= hip.backend.dims.queue_cap == 12, (seed, t)
+            assert int(np.count_nonzero(hip.backend.get("ERROR"))) == 0, (seed, t)
             assert r_hip[1] == r_cpu[1] and r_hip[2] == r_cpu[2] and r_hip[3] == r_cpu[3], (seed, t)
             for name in r_cpu[0]:
                 for key in ("agent_position", "agent_caps", "alloc_task", "mask", "legal_mask", "event_flags"):
