@@ -576,8 +576,16 @@ int muavta_set_state(MuavtaEnv* env, const void* src, size_t bytes);
 int muavta_lsap(int32_t device, const double* cost, int32_t n, int32_t nr, int32_t nc, int64_t* row, int64_t* col);
 /* Same, with the solver named: the allocator path uses MUAVTA_LSAP_REGISTERS (rows <= 32, columns <= 64 after scipy's
  * transpose; no LDS traffic inside the solve) and MUAVTA_LSAP_LDS beyond that (64 x 128); MUAVTA_LSAP_AUTO picks by size.
- * Both are the same algorithm with the same tie rule; the entry point exists so that tests can pin each one. */
-enum { MUAVTA_LSAP_AUTO = 0, MUAVTA_LSAP_LDS = 1, MUAVTA_LSAP_REGISTERS = 2 };
+ * Both are the same algorithm with the same tie rule; the entry point exists so that tests can pin each one.
+ * MUAVTA_LSAP_TILE16 / _TILE24 / _TILE64 run the solver of an environment tile itself, for problems of at most 16 x 40 / 24 x 48 /
+ * 64 x 128 (min(n_rows, n_cols) x max(n_rows, n_cols), i.e. after scipy's transpose); a larger problem is MUAVTA_E_ARG.  What they are:
+ * the template instantiation the environment kernels use for that tile — the same register layout of a cost column (one 16-row tuple;
+ * 16 + 8 rows; four tuples), the same row count and scratch array sizes — on the route the allocator takes: cost columns in registers
+ * while they fit one per lane (always on the first two, up to 64 columns on the 64-agent tile), the solver that evaluates cost elements
+ * when it scans them beyond that.  What they are not: the code the rollout runs.  They are compiled as a kernel of their own, which reads
+ * each cost from the caller's matrix; the copies inlined into the fused rollout / allocate kernels remain checked by the simulation's
+ * comparison with the reference. */
+enum { MUAVTA_LSAP_AUTO = 0, MUAVTA_LSAP_LDS = 1, MUAVTA_LSAP_REGISTERS = 2, MUAVTA_LSAP_TILE16 = 3, MUAVTA_LSAP_TILE24 = 4, MUAVTA_LSAP_TILE64 = 5 };
 int muavta_lsap_impl(int32_t device, const double* cost, int32_t n_problems, int32_t n_rows, int32_t n_cols, int64_t* row_ind,
                      int64_t* col_ind, int32_t impl);
 

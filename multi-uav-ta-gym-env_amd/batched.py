@@ -891,9 +891,15 @@ class BatchedMultiUAVEnv:
         return {k: p.value for k, p in zip(keys, ptrs)}
 
 
+LSAP_IMPLS = {"auto": 0, "lds": 1, "registers": 2, "tile16": 3, "tile24": 4, "tile64": 5}  # include/muavta.h: MUAVTA_LSAP_*
+
+
 def lsap(cost: np.ndarray, device: int = 0, impl: str = "auto"):
     """Batched scipy-compatible linear_sum_assignment on the GPU: cost [n, nr, nc] (or [nr, nc]).
-    impl: 'auto' | 'lds' (64 x 128 solver) | 'registers' (the allocator path's solver, up to 32 x 64)."""
+    impl: 'auto' | 'lds' (64 x 128 solver) | 'registers' (the allocator path's solver, up to 32 x 64) |
+    'tile16' | 'tile24' | 'tile64': the solver of that environment tile itself — the instantiation its kernels use, built as a kernel
+    of its own — for min(nr, nc) x max(nr, nc) up to 16 x 40 / 24 x 48 / 64 x 128 (register cost columns up to 64 columns on tile64,
+    costs evaluated when scanned beyond).  A problem beyond the named solver's limit raises MuavtaError."""
     c = np.ascontiguousarray(cost, dtype=np.float64)
     single = c.ndim == 2
     if single:
@@ -903,7 +909,7 @@ def lsap(cost: np.ndarray, device: int = 0, impl: str = "auto"):
     row = np.empty((n, m), dtype=np.int64)
     col = np.empty((n, m), dtype=np.int64)
     L = native.lib()
-    rc = L.muavta_lsap_impl(int(device), _vp(c), n, nr, nc, _vp(row), _vp(col), {"auto": 0, "lds": 1, "registers": 2}[impl])
+    rc = L.muavta_lsap_impl(int(device), _vp(c), n, nr, nc, _vp(row), _vp(col), LSAP_IMPLS[impl])
     if rc != 0:
         raise MuavtaError(f"muavta_lsap failed ({rc}): {L.muavta_last_error(None).decode()}")
     return (row[0], col[0]) if single else (row, col)

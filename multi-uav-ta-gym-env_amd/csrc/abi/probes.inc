@@ -39,8 +39,16 @@ int muavta_lsap_impl(int32_t device, const double* cost, int32_t n, int32_t nr, 
   for (size_t i = 0, m = (size_t)n * nr * nc; i < m; i++)
     if (std::isnan(cost[i]) || cost[i] == -INFINITY) { g_create_error = "muavta_lsap: matrix contains invalid numeric entries (NaN or -inf)"; return MUAVTA_E_ARG; }
   const bool fits_reg = mn <= TileLsapReg::A && mx <= TileLsapReg::T;
-  if (impl < MUAVTA_LSAP_AUTO || impl > MUAVTA_LSAP_REGISTERS || (impl == MUAVTA_LSAP_REGISTERS && !fits_reg)) {
+  if (impl < MUAVTA_LSAP_AUTO || impl > MUAVTA_LSAP_TILE64 || (impl == MUAVTA_LSAP_REGISTERS && !fits_reg)) {
     g_create_error = "muavta_lsap_impl: unknown solver, or problem beyond 32 x 64 for the register solver"; return MUAVTA_E_ARG;
+  }
+  // the env tiles' own solvers: min(nr, nc) <= agents, max(nr, nc) <= task slots of the tile
+  const int tile_a = impl == MUAVTA_LSAP_TILE16 ? Tile16::A : impl == MUAVTA_LSAP_TILE24 ? Tile24::A : Tile64::A;
+  const int tile_t = impl == MUAVTA_LSAP_TILE16 ? Tile16::T : impl == MUAVTA_LSAP_TILE24 ? Tile24::T : Tile64::T;
+  if (impl >= MUAVTA_LSAP_TILE16 && (mn > tile_a || mx > tile_t)) {
+    g_create_error = "muavta_lsap_impl: problem beyond " + std::to_string(tile_a) + " x " + std::to_string(tile_t) + " for the " +
+                     std::to_string(tile_a) + "-agent tile's solver";
+    return MUAVTA_E_ARG;
   }
   const bool use_reg = impl == MUAVTA_LSAP_REGISTERS || (impl == MUAVTA_LSAP_AUTO && fits_reg);
   DeviceScope scope_(device);
@@ -48,7 +56,17 @@ int muavta_lsap_impl(int32_t device, const double* cost, int32_t n, int32_t nr, 
   size_t cb = (size_t)n * nr * nc * sizeof(double), rb = (size_t)n * mn * sizeof(int64_t);
   CK(dc.alloc(cb)); CK(dr.alloc(rb)); CK(dcl.alloc(rb)); CK(dst.alloc((size_t)n * sizeof(int32_t)));
   CK(hipMemcpy(dc, cost, cb, hipMemcpyHostToDevice));
-  if (use_reg) {
+  auto launch_tile = [&](auto tile) -> hipError_t {  // k_lsap_tile<TL> for the env tile type of `tile`
+    typedef decltype(tile) TL;
+    size_t lds = Lds<TL>::bytes();
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lsap_tile<TL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+    hipLaunchKernelGGL((k_lsap_tile<TL>), dim3(n), dim3(WG), lds, 0, dc.p, nr, nc, dr.p, dcl.p, dst.p);
+    return hipSuccess;
+  };
+  if (impl == MUAVTA_LSAP_TILE16) { CK(launch_tile(Tile16())); }
+  else if (impl == MUAVTA_LSAP_TILE24) { CK(launch_tile(Tile24())); }
+  else if (impl == MUAVTA_LSAP_TILE64) { CK(launch_tile(Tile64())); }
+  else if (use_reg) {
     size_t lds = Lds<TileLsapReg>::bytes();
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lsap<TileLsapReg, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_lsap<TileLsapReg, true>), dim3(n), dim3(WG), lds, 0, dc.p, nr, nc, dr.p, dcl.p, dst.p);

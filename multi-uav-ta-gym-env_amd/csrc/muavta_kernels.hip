@@ -8,6 +8,7 @@
 //   k_rollout   [reset] + n x (allocate -> step) in ONE launch, blob never leaves LDS in between
 //   k_metrics   calculate_metrics for every env
 //   k_lsap / k_avoid   stand-alone solver / obstacle-avoidance entry points
+//   k_lsap_tile        the stand-alone solver built from an env tile's own Sim<TL> (muavta_lsap_impl: MUAVTA_LSAP_TILE16 / 24 / 64)
 // There is no CPU fallback: without a HIP device every entry point fails with MUAVTA_E_NO_DEVICE.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -895,6 +896,19 @@ __global__ __launch_bounds__(WG) void k_call(const DevCtx* __restrict__ ctxp, Ca
 // REG: the register-resident solver of the allocator path (rows <= 32, columns <= 64); else the LDS solver (64 x 128).
 typedef Tile<32, 64, 16, 16, 16, 8> TileLsapReg;
 typedef Tile<64, 128, 16, 16, 16, 8> TileLsapLds;  // keeps the full cost tile in LDS (the env's 64x128 tile evaluates costs on the fly)
+// What a stand-alone solve reports (lane 0): the status word, and the assignment in scipy's output form — rows ascending, min(nr, nc) pairs
+template <class TL>
+__device__ __forceinline__ void lsap_probe_out(const Lds<TL>& L, int prob, int nr, int nc, int64_t* row, int64_t* col, int32_t* status) {
+  if (threadIdx.x != 0) return;
+  const bool tr = nc < nr;
+  const int Rr = tr ? nc : nr;
+  status[prob] = L.S->error;  // MUAVTA_ERR_LSAP: no finite assignment (scipy: "cost matrix is infeasible")
+  int64_t* r = row + (size_t)prob * Rr;
+  int64_t* cc = col + (size_t)prob * Rr;
+  int n = 0;
+  if (!tr) { for (int i = 0; i < nr; i++) { r[n] = i; cc[n] = L.X->col4row[i]; n++; } }
+  else { for (int i = 0; i < nr; i++) if (L.X->row4col[i] >= 0) { r[n] = i; cc[n] = L.X->row4col[i]; n++; } }
+}
 template <class TL, bool REG>
 __global__ __launch_bounds__(WG) void k_lsap(const double* cost, int nr, int nc, int64_t* row, int64_t* col, int32_t* status) {
   Lds<TL> L(smem);
@@ -911,14 +925,36 @@ __global__ __launch_bounds__(WG) void k_lsap(const double* cost, int nr, int nc,
   if (threadIdx.x == 0) L.S->error = 0;
   lds_sync();
   if constexpr (REG) sim.lsap_reg(Rr, Cc); else sim.lsap(Rr, Cc);
-  if (threadIdx.x == 0) {
-    status[prob] = L.S->error;  // MUAVTA_ERR_LSAP: no finite assignment (scipy: "cost matrix is infeasible")
-    int64_t* r = row + (size_t)prob * Rr;
-    int64_t* cc = col + (size_t)prob * Rr;
-    int n = 0;
-    if (!tr) { for (int i = 0; i < nr; i++) { r[n] = i; cc[n] = L.X->col4row[i]; n++; } }
-    else { for (int i = 0; i < nr; i++) if (L.X->row4col[i] >= 0) { r[n] = i; cc[n] = L.X->row4col[i]; n++; } }
+  lsap_probe_out(L, blockIdx.x, nr, nc, row, col, status);
+}
+
+// Stand-alone LSAP on an ENV tile (Tile16 / Tile24 / Tile64): Sim<TL> over Lds<TL> for the tile type the env kernels are built from — the
+// same CostCol layout, row count and scratch array sizes — along the route Sim::allocate takes: cost columns in registers + lsap_reg_solve
+// while the columns fit the wave, the on-the-fly lsap(nr, nc, cost_at) beyond that (Tile64).  These tiles hold no A x T cost tile in LDS, so
+// each cost element is read from the global input (transposed index when nc < nr).  A kernel of its own: the copies of the solver inlined
+// into k_rollout / k_allocate are checked by the simulation-against-oracle tests, not by this probe.
+template <class TL>
+__global__ __launch_bounds__(WG) void k_lsap_tile(const double* cost, int nr, int nc, int64_t* row, int64_t* col, int32_t* status) {
+  Lds<TL> L(smem);
+  DevParams dummy;
+  Sim<TL> sim(*L.S, *reinterpret_cast<EnvCold<TL>*>(L.S) /* never touched by the solver */, *L.X, dummy, nullptr);
+  const int prob = blockIdx.x;
+  const double* c = cost + (size_t)prob * nr * nc;
+  const bool tr = nc < nr;
+  const int Rr = tr ? nc : nr, Cc = tr ? nr : nc;
+  auto cost_at = [c, nc, tr](int i, int j) -> double { return tr ? c[j * nc + i] : c[i * nc + j]; };  // element (i, j) of scipy's (possibly transposed) matrix
+  if (threadIdx.x == 0) L.S->error = 0;
+  lds_sync();
+  const bool reg_cols = TL::REGC && (TL::T <= WG || Cc <= WG);  // (Sim::allocate's condition)
+  if (reg_cols) {
+    const int lane = sim.lane;
+    typename Sim<TL>::CostCol cc;
+    sim.build_cols(cc, Rr, [&](int i) -> double { return lane < Cc ? cost_at(i, lane) : 0.0; });
+    sim.lsap_reg_solve(Rr, Cc, [&](int i) -> double { return cc.get(i); });
+  } else if constexpr (TL::OTFC) {
+    sim.lsap(Rr, Cc, cost_at);
   }
+  lsap_probe_out(L, blockIdx.x, nr, nc, row, col, status);
 }
 
 __global__ void k_domain_math(const double* x, const double* y, int n, double* out_sqrt, double* out_div, double* out_div2) {

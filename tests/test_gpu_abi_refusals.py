@@ -243,6 +243,11 @@ def test_every_refusal_returns_its_code_and_leaves_the_handle_untouched():
     assert L.muavta_lsap_impl(0, _vp(cost), 0, 2, 2, _vp(row), _vp(col), 0) == E_ARG
     assert L.muavta_lsap_impl(0, _vp(cost), 1, 65, 129, _vp(row), _vp(col), 0) == E_ARG
     assert L.muavta_lsap_impl(0, _vp(cost), 1, 33, 64, _vp(row), _vp(col), 2) == E_ARG
+    for nr, nc, impl, limit in ((17, 40, 3, "16 x 40"), (16, 41, 3, "16 x 40"), (25, 48, 4, "24 x 48")):  # an env tile's solver, one past its limit
+        assert L.muavta_lsap_impl(0, _vp(cost), 1, nr, nc, _vp(row), _vp(col), impl) == E_ARG
+        assert limit in L.muavta_last_error(None).decode()
+    assert L.muavta_lsap_impl(0, _vp(cost), 1, 2, 2, _vp(row), _vp(col), 6) == E_ARG
+    assert "unknown solver" in L.muavta_last_error(None).decode()
     cost[3] = np.nan
     assert L.muavta_lsap_impl(0, _vp(cost), 1, 2, 2, _vp(row), _vp(col), 0) == E_ARG
     assert "invalid numeric" in L.muavta_last_error(None).decode()
