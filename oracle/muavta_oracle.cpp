@@ -2092,6 +2092,19 @@ int orc_get_escorts(void* h, int32_t* out, int cap) {  // _escort_by_recon in in
   for (auto& p : e->escort_by_recon) { if (n >= cap) break; out[2 * n] = p.first; out[2 * n + 1] = p.second; n++; }
   return n;
 }
+// lengths of the lists the device keeps in fixed tiles: event_list (events generated since the last drain, out-of-step calls included),
+// pending_reveals, _escort_by_recon, and the task ids a slot has to be kept for (not retired, or still queued by a live agent)
+void orc_list_sizes(void* h, int32_t* out) {
+  Env* e = (Env*)h;
+  out[0] = (int)e->event_list.size(); out[1] = (int)e->pending_reveals.size(); out[2] = (int)e->escort_by_recon.size();
+  int held = 0;
+  for (size_t k = 1; k < e->tasks.size(); k++) {
+    bool keep = e->tasks[k].status != 2;
+    for (auto& a : e->agents) if (!keep && a.state != -1 && Env::in_queue(a, (int)k)) keep = true;
+    held += keep;
+  }
+  out[3] = held;
+}
 void orc_get_open(void* h, int32_t* ids) { Env* e = (Env*)h; for (size_t i = 0; i < e->last_tasks_info.size(); i++) ids[i] = e->last_tasks_info[i]; }
 void orc_get_events(void* h, int32_t* ev) { Env* e = (Env*)h; for (size_t i = 0; i < e->done_events.size(); i++) { ev[2 * i] = e->done_events[i].tag; ev[2 * i + 1] = e->done_events[i].arg; } }
 void orc_get_actions(void* h, int32_t* out) { Env* e = (Env*)h; for (size_t i = 0; i < e->last_actions.size(); i++) { out[2 * i] = e->last_actions[i].first; out[2 * i + 1] = e->last_actions[i].second; } }

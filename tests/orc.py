@@ -62,6 +62,13 @@ class OracleEnv:
                 "n_replans", "time_steps", "n_pending", "n_reached", "pending_reset", "terminated", "truncated", "max_queue"]
         return dict(zip(keys, d.tolist()))
 
+    def list_sizes(self):
+        """Current lengths of the lists a device tile bounds: event_list (since the last drain), pending_reveals, _escort_by_recon, and the
+        task ids a device slot is held for (not retired, or still queued by a live agent)."""
+        d = np.zeros(4, dtype=np.int32)
+        self.L.orc_list_sizes(self.h, _p(d))
+        return dict(zip(["n_event_list", "n_pending", "n_escorts", "n_held"], d.tolist()))
+
     def allocate(self, interval, use_vis=1):
         aa = np.full(self.A + 1, -1, dtype=np.int32)
         ai = np.zeros(self.A + 1, dtype=np.int32)
