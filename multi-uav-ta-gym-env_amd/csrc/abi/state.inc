@@ -28,6 +28,9 @@ int gather(MuavtaEnv* e, MuavtaField f, void* dst, size_t bytes, bool scatter) {
   auto QS = [&](int n) -> QueueSide<TL::A, TL::T, true>& {  // where this tile keeps next_free_* / orgReqs / doneReqs
     if constexpr (TL::SLIM) return static_cast<QueueSide<TL::A, TL::T, true>&>(cold[n]); else return static_cast<QueueSide<TL::A, TL::T, true>&>(blobs[n]);
   };
+  auto TT = [&](int n) -> TaskTimes<TL::T, true>& {  // where this tile keeps initTime / doneTime
+    if constexpr (TL::TIMES_LDS) return static_cast<TaskTimes<TL::T, true>&>(blobs[n]); else return static_cast<TaskTimes<TL::T, true>&>(cold[n]);
+  };
 #define BAD() do { e->err = "muavta_get/set: buffer size mismatch, need " + std::to_string(need) + " bytes"; return MUAVTA_E_ARG; } while (0)
 #define RW(dstv, srcv) do { if (scatter) (srcv) = (dstv); else (dstv) = (srcv); } while (0)
   switch (f) {
@@ -114,7 +117,7 @@ int gather(MuavtaEnv* e, MuavtaField f, void* dst, size_t bytes, bool scatter) {
       break;
     case MUAVTA_F_TASK_TIMES:
       if (!chk((size_t)N * T * 2 * 8)) BAD();
-      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) { RW(D[((size_t)n * T + s) * 2], cold[n].t_init[s]); RW(D[((size_t)n * T + s) * 2 + 1], cold[n].t_dtime[s]); }
+      for (int n = 0; n < N; n++) for (int s = 0; s < T; s++) { RW(D[((size_t)n * T + s) * 2], TT(n).t_init[s]); RW(D[((size_t)n * T + s) * 2 + 1], TT(n).t_dtime[s]); }
       break;
     case MUAVTA_F_TASK_META:
       if (!chk((size_t)N * T * 8 * 4)) BAD();

@@ -252,6 +252,10 @@ struct Sim {
   DEV QueueSide<A, T, true>& qs() const {
     if constexpr (TL::SLIM) return static_cast<QueueSide<A, T, true>&>(C); else return static_cast<QueueSide<A, T, true>&>(S);
   }  // after the blob was (re)loaded or reset behind this object's back
+  // initTime / doneTime of the tasks: LDS or the HBM record, by tile (TaskTimes in muavta_state.h)
+  DEV TaskTimes<T, true>& times() const {
+    if constexpr (TL::TIMES_LDS) return static_cast<TaskTimes<T, true>&>(S); else return static_cast<TaskTimes<T, true>&>(C);
+  }
 
   DEV void fail(int code) { if (S.error == 0) S.error = code; }
   // S.obs_rows = (rows of the handle's task tensor from which on pad rows are known to be there) | OBS_STATIC, or -1 (unknown).

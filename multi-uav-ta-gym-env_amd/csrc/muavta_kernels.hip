@@ -290,6 +290,7 @@ __global__ __launch_bounds__(WG, TILE_MIN_WAVES(TL)) void k_step(const DevCtx* _
 }
 
 enum { SCORED_EXTRA_LDS = 128 };  // allocate<true>'s task list: one byte per slot, behind the tile
+static_assert(Lds<Tile16>::bytes() + SCORED_EXTRA_LDS <= 10240, "k_run / k_rl_step / the learned policies' rollouts of Tile16 no longer fit 16 workgroups per CU");
 // The allocator a k_allocate / k_rollout instantiation runs, as ONE tag type: the Hungarian family and the classical baselines pick their
 // variant from the run-time `mode`; a learned policy is named by its traits (muavta_device.h).  A tag gives the LDS its kernels need behind
 // the tile (allocate<true>'s task list) and the waves per SIMD its rollout is built for.  A fourth learned policy is a traits type next to
@@ -763,6 +764,10 @@ __global__ __launch_bounds__(WG) void k_observe(const DevCtx* __restrict__ ctxp)
     EnvState<TL>* blob = blob_of<TL>(ctx, env);   // task times it rebuilt on the way (refresh_task_times)
     blob->obs_rows = L.S->obs_rows;
     blob->times_dirty = L.S->times_dirty;
+  }
+  if constexpr (TL::TIMES_LDS) {  // (those times are part of the record on this tile, not of the HBM part the rebuild wrote in place)
+    EnvState<TL>* blob = blob_of<TL>(ctx, env);
+    for (int s = threadIdx.x; s < TL::T; s += WG) { blob->t_init[s] = L.S->t_init[s]; blob->t_dtime[s] = L.S->t_dtime[s]; }
   }
 }
 

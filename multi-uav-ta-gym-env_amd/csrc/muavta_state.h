@@ -56,8 +56,9 @@ struct DevParams {
   int32_t rw_plain;               // every reward weight is finite and >= 0 and reward_norm_factor > 0: a step whose reward terms are all +0.0 has reward +0.0
 };
 
-template <int A_, int T_, int H_, int R_, int E_, int Q_, bool REGC_ = false, bool OTFC_ = false, bool SLIM_ = false>
+template <int A_, int T_, int H_, int R_, int E_, int Q_, bool REGC_ = false, bool OTFC_ = false, bool SLIM_ = false, bool TIMES_LDS_ = false>
 struct Tile {
+  static constexpr bool TIMES_LDS = TIMES_LDS_;  // initTime / doneTime of the tasks live in LDS instead of the HBM record (TaskTimes below): the tiles with room for 16 x T more bytes
   static constexpr bool SLIM = SLIM_;  // next_free_* / orgReqs / doneReqs / mission areas live in the HBM record instead of LDS (the 24-agent tile: 16 envs per CU need <= 10 KiB)
   static constexpr bool REGC = REGC_;  // the allocator builds the LSAP cost columns in registers (while they fit one per lane): no A x T cost tile in LDS
   static constexpr bool OTFC = OTFC_;  // beyond 64 columns the (LDS) solver evaluates cost elements on the fly: no A x T cost tile either
@@ -100,22 +101,32 @@ template <int A, int T, bool HERE> struct QueueSide {
 };
 template <int A, int T> struct QueueSide<A, T, false> {};
 
+// Task.initTime / doneTime: rebuilt when an allocation changed (refresh_task_times), read by the observation rows of EVERY step
+// (columns 16 / 17 move with t).  In LDS where the tile has room at its residency (TL::TIMES_LDS), so that the light pass of the
+// observation writer has no memory operand on the step's chain; in the HBM record elsewhere.  Reached through Sim::times().
+template <int T, bool HERE> struct TaskTimes {
+  double t_init[T], t_dtime[T];  // initTime, doneTime
+};
+template <int T> struct TaskTimes<T, false> {};
+
 // Part of an env that lives in HBM only (one record per env, L2-resident while the rollout runs): the six-component
-// requirement vectors of the tasks, the per-queue-entry travel times and the derived init/done times — touched when an
+// requirement vectors of the tasks, the per-queue-entry travel times and (unless TL::TIMES_LDS) the derived init/done times — touched when an
 // allocation changes, when a task is created or concluded, and by the observation / token writers (all lanes, coalesced
 // within a row), never by the per-step movement / sensing / threat phases.  Keeping them out of LDS is what lets 16 envs
 // of the 16-agent tile share one CU's 160 KiB.
-template <class TL>
-struct alignas(16) EnvCold : QueueSide<TL::A, TL::T, TL::SLIM> {
-  enum { A = TL::A, T = TL::T, Q = TL::Q };
+template <int T> struct TaskReqs {
   double t_cur[6][T], t_alloc[6][T];  // currentReqs, allocatedReqs
-  double t_init[T], t_dtime[T];       // initTime, doneTime
+};
+// (bases in the order the record has always had: where the times stay in HBM no field moves)
+template <class TL>
+struct alignas(16) EnvCold : QueueSide<TL::A, TL::T, TL::SLIM>, TaskReqs<TL::T>, TaskTimes<TL::T, !TL::TIMES_LDS> {
+  enum { A = TL::A, T = TL::T, Q = TL::Q };
   double a_qtime[A][Q];               // allocationDetails[agent][1] (time_to_task) of each queued task
   double obst[8][3];                  // obstacles (x, y, size): only with num_obstacles > 0
 };
 
 template <class TL>
-struct alignas(16) EnvState : QueueSide<TL::A, TL::T, !TL::SLIM> {
+struct alignas(16) EnvState : QueueSide<TL::A, TL::T, !TL::SLIM>, TaskTimes<TL::T, TL::TIMES_LDS> {
   enum { A = TL::A, T = TL::T, H = TL::H, R = TL::R, E = TL::E, Q = TL::Q, KW = TL::KW };
   // ---- 8-byte arrays --------------------------------------------------------------------------
   double a_px[A], a_py[A];          // position
@@ -191,7 +202,13 @@ struct alignas(16) EnvState : QueueSide<TL::A, TL::T, !TL::SLIM> {
 // creating arrivals for a 16-UAV config (DroneEnv.py:145-147,1646-1689: len(tasks) >= max_tasks - 1) — and queues of 10:
 // with 32 slots / queue 8 about 1 in 10,000 seeds of WPS_hard_x2 overflowed (34 slots); events <= 16, pending reveals <= 22
 // measured over 4096 seeds.
-typedef Tile<16, 40, 16, 48, 40, 10, true> Tile16;
+// MUAVTA_TIMES_LDS (1): initTime / doneTime of the 16-agent tile in LDS — 640 of the 1,120 B the tile leaves unused at 16 envs
+// per CU (10 KiB each).  0 puts them back into the HBM record (9,120 B per env; a five-wave build needs <= 8 KiB).  The 24-agent
+// tile has 16 B to spare and keeps them in HBM.
+#ifndef MUAVTA_TIMES_LDS
+#define MUAVTA_TIMES_LDS 1
+#endif
+typedef Tile<16, 40, 16, 48, 40, 10, true, false, false, MUAVTA_TIMES_LDS != 0> Tile16;
 #ifndef MUAVTA_TILE24_SLIM  // experiment knob (0: QueueSide in LDS like the other tiles: 11.6 KB per env, 14 envs per CU)
 #define MUAVTA_TILE24_SLIM 1
 #endif

@@ -173,7 +173,7 @@
         r[4] = (S.t_flags[s] & TF_DEADLINE) ? S.t_deadline[s] : -1; r[5] = S.t_created[s]; r[6] = S.t_required[s];
         r[7] = (S.t_flags[s] & TF_ESCORT) ? 1 : 0; r[8] = S.t_ndet[s]; r[9] = S.t_prot_agent[s];
         r[10] = (S.t_flags[s] & TF_ELIGIBLE) ? (double)S.t_elig[s] : -1.0; r[11] = S.t_px[s]; r[12] = S.t_py[s];
-        r[13] = qs().t_org[s]; r[14] = qs().t_done[s]; r[15] = C.t_init[s]; r[16] = C.t_dtime[s];
+        r[13] = qs().t_org[s]; r[14] = qs().t_done[s]; r[15] = times().t_init[s]; r[16] = times().t_dtime[s];
         for (int c = 0; c < 6; c++) { r[17 + c] = C.t_cur[c][s]; r[23 + c] = C.t_alloc[c][s]; }
       }
     }
@@ -258,7 +258,7 @@
     C.t_cur[type][s] = req;
     obs_static_clear();
     qs().t_org[s] = req; qs().t_done[s] = 0;
-    C.t_init[s] = -1; C.t_dtime[s] = -1;
+    times().t_init[s] = -1; times().t_dtime[s] = -1;
     S.t_status[s] = 0; S.t_type[s] = type; S.t_created[s] = 0; S.t_deadline[s] = -1; S.t_required[s] = 0;
     S.t_flags[s] = 0; S.t_elig[s] = 0; S.t_threat[s] = -1;
     S.t_prot_agent[s] = -1; S.t_prot_id[s] = -1; S.t_prot_slot[s] = -1;

@@ -95,7 +95,7 @@
           ti = __longlong_as_double((long long)tmin[s]);
           td = __longlong_as_double((long long)tmax[s]) + (double)task_duration(S.t_type[s]);
         }
-        C.t_init[s] = ti; C.t_dtime[s] = td;
+        times().t_init[s] = ti; times().t_dtime[s] = td;
       } else { ti = -1; td = -1; }  // retired / free slots: no observation row reads them
       tt[s] = ti; tt[T + s] = td;
     }
@@ -121,7 +121,7 @@
     // (r4) LIGHT pass: the handle's buffer already holds the static columns of every open row (OBS_STATIC: no requirement /
     // allocation vector and no open-list change since the last write) — only the columns that move every step are rewritten:
     // position (Int and escort tasks follow their threat / UAV), status, init / end time (relative to t), age.  6 stores and 2
-    // HBM operands per row instead of 21 and 16.
+    // HBM operands per row (none where the task times live in LDS: TL::TIMES_LDS) instead of 21 and 16.
     const bool light = o_tasks != nullptr && obs_state > 0 && (obs_state & OBS_STATIC) != 0;
     // The HBM rows of the first 64 observation rows are requested NOW, so that their latency runs under the rebuild of the
     // task times below (LDS work); (initTime, doneTime) then come from the scratch tile when they were rebuilt.
@@ -131,7 +131,7 @@
       const int s0 = lane < n ? (int)S.open_slot[lane] : 0;
 #pragma unroll
       for (int c = 0; c < 6; c++) { pc[c] = lane < n ? C.t_cur[c][s0] : 0.0; pa[c] = lane < n ? C.t_alloc[c][s0] : 0.0; }
-      if (!dirty && lane < n) { pti = C.t_init[s0]; ptd = C.t_dtime[s0]; }
+      if (!dirty && lane < n) { pti = times().t_init[s0]; ptd = times().t_dtime[s0]; }
     }
     refresh_task_times();
     const double mts = (double)(P.max_time_steps > 1 ? P.max_time_steps : 1), inv_mts = P.inv_mts;
@@ -157,9 +157,10 @@
         ty = S.t_type[s];
         typemask = (S.t_flags[s] & TF_ELIGIBLE) ? S.t_elig[s] : 0xffffffffu;
         if (light) {  // (uniform)
-          // (OBS_STATIC implies the task times are not dirty.  These two HBM operands sit on the step's chain: a build without them ran
-          // 1.2 % faster, requesting them at the start of step() instead won back 0.3 % — within noise, not adopted: profiles/r04_ab_obs_light_prefetch.txt)
-          const double ti = C.t_init[s], td = C.t_dtime[s];
+          // (OBS_STATIC implies the task times are not dirty.  As HBM operands these two sat on the step's chain: a build without them ran
+          // 1.2 % faster, requesting them at the start of step() instead won back 0.3 % — profiles/r04_ab_obs_light_prefetch.txt.  With
+          // TL::TIMES_LDS they are LDS reads and this pass has no memory operand: +1.8 % on the headline, profiles/r07_step_chain_ab.json)
+          const double ti = times().t_init[s], td = times().t_dtime[s];
           if (P.saturate_mask && C.t_alloc[ty][s] >= qs().t_org[s]) typemask = 0;
           uint32_t off = ju * 4u;
           const uint32_t cstride = (uint32_t)MT * 4u;
@@ -190,7 +191,7 @@
         } else {
 #pragma unroll
           for (int c = 0; c < 6; c++) { cur[c] = C.t_cur[c][s]; alc[c] = C.t_alloc[c][s]; }
-          if (dirty) { ti = obs_times()[s]; td = obs_times()[T + s]; } else { ti = C.t_init[s]; td = C.t_dtime[s]; }
+          if (dirty) { ti = obs_times()[s]; td = obs_times()[T + s]; } else { ti = times().t_init[s]; td = times().t_dtime[s]; }
         }
 #pragma unroll
         for (int c = 0; c < 6; c++) { r[4 + c] = (float)cur[c]; r[10 + c] = (float)alc[c]; }
