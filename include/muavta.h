@@ -158,6 +158,7 @@ typedef enum MuavtaField {
                                                        currentReqs[6], allocatedReqs[6]                              (read-only) */
   MUAVTA_F_KNOWN_COUNT,        /* i32 [N, A]         len(agent_known_tasks[a]) incl. ids of released tasks (read-only)  */
   MUAVTA_F_ESCORTS,            /* i32 [N, tile_agents, 2]  env._escort_by_recon in insertion order: (recon UAV.id, escort Task.id), -1 padded (read-only) */
+  MUAVTA_F_TOKEN_PADS,         /* i32 [2]            (max_tasks, max_agents) of the pair-cost planners: a setting of the HANDLE, not a per-env array — see "The TOKEN PADS" below (rw) */
   MUAVTA_F_COUNT_
 } MuavtaField;
 
@@ -280,7 +281,8 @@ int muavta_set_allocator(MuavtaEnv* env, int32_t mode);
  * layer 3 (n-ascending from the bias) as above; score = 1.0f / (1.0f + expf(-fminf(fmaxf(logit, -20.0f), 20.0f))) in float32 with a
  * correctly rounded division; score_clamp is IGNORED.  Pairs that are pad or whose edge_valid is 0 are not evaluated and report 0;
  * equal token rows in one env give bit-equal scores; no value crosses lanes inside a pair's chains.
- * Shapes of muavta_pair_scores(_device) by installed kind: MLP-Pair and MLP-ContextPair [N, 16, 32]; MLP-Coalition [N, 16, 48]. */
+ * Shapes of muavta_pair_scores(_device) by installed kind: MLP-Pair and MLP-ContextPair [N, 16, 32] — [N, 48, 64] while the wide
+ * token pads are set (MUAVTA_F_TOKEN_PADS below); MLP-Coalition [N, 16, 48] whatever the pads. */
 typedef struct MuavtaPairMlp {
   int32_t raw_features, hidden;  /* raw_features: the MUAVTA_TOK_* kind (0, 1: MLP-Pair, hidden 128; 2: MLP-Coalition, hidden 256) */
   float score_clamp;             /* (ignored by an MLP-Coalition) */
@@ -290,6 +292,32 @@ int muavta_set_pair_policy(MuavtaEnv* env, const MuavtaPairMlp* spec);
 int muavta_pair_scores(MuavtaEnv* env, float* scores, float* logits);
 int muavta_pair_scores_device(MuavtaEnv* env, float* scores, float* logits);
 
+/* The TOKEN PADS of the pair-cost planners (field MUAVTA_F_TOKEN_PADS of muavta_set / muavta_get: i32 [2], 8 bytes; the C ABI's entry points
+ * are a frozen set, so the setting travels through the field accessors): the (max_tasks, max_agents) their reference classes are built with —
+ * UrgencyPair(max_tasks, max_agents) (TaskAllocation/Hybrid/PairCostHybrid.py:520-530), PairCostHybrid(..., max_tasks, max_agents)
+ * (:154-197) and the matching ContextPairHybrid (ContextPairHybrid.py:154-210).  Exactly two values are legal, the two grids the
+ * reference's harness has (experiments/wps_eval.py:422-434):
+ *   (32, 16)   the default (PairCostHybrid.py:26-27), and what every handle computed before this setting existed, bit for bit;
+ *   (64, 48)   the scaled pads of the suites WPS_attn_L / _XL / _OS18 / _OS24, WPS_scale and WPS_oversized.
+ * Honoured by MUAVTA_ALLOC_URGENCY_PAIR and by MUAVTA_ALLOC_MLP_PAIR with an MLP-Pair or MLP-ContextPair installed, on every path those
+ * modes run (muavta_rollout, muavta_allocate(_part) / muavta_step_staged, sub-batch parts, both state lanes) and by
+ * muavta_pair_scores(_device).  Semantics, as the reference's (PairCostHybrid.py:31-86): the task list handed to the allocator is the
+ * first max_tasks underfilled tasks; scores exist for the first max_agents live agents x those tasks, on edge_valid pairs only; the
+ * scarcity term's n_live is the whole live fleet.  The learned kinds keep their networks, weights and arithmetic contract word for
+ * word; a_pool then runs over up to 48 agent rows, t_pool over up to 64 task rows, context = muavta_context(kind, 64, .).  A tile
+ * with fewer agent rows or task slots than the pads (24 x 48) sees the surplus as pad rows; they cost no forward-pass work.
+ * NOT affected: MLP-Coalition keeps its own 16 x 48 escort grid (build_escort_tokens(env, 48, 16)) and MUAVTA_ALLOC_URGENCY_COALITION has
+ * no pads; installing or selecting either while wide pads are set changes nothing about them.  muavta_allocate_scored, muavta_tokens
+ * and muavta_context take their pads as arguments, as before.
+ * The call is ordered behind every launch already queued on the handle (both state lanes, sub-batch streams), as muavta_set_pair_policy
+ * is: the pads select the kernels of the launches queued AFTER it, what is already queued keeps its own, and with a policy installed the
+ * call waits for the lanes' streams before it moves the policy to the other scratch block.  A second lane created later carries the pads.  The per-env scratch block of the learned kinds at wide pads
+ * (about 37 KB) is allocated when wide pads first meet an installed policy.  Any other pair: MUAVTA_E_ARG.  Wide pads on a tile with
+ * 16 agent rows (16 x 40, 16 x 48): MUAVTA_E_ARG — those tiles' kernels keep compile-time pads; run the case on the 24 x 48 tile
+ * through MuavtaParams.tile_agents / tile_tasks / tile_threats (Python: the tile override of params_for_case).
+ * muavta_get(env, MUAVTA_F_TOKEN_PADS, dst, 8) reads the setting back; either call with another size: MUAVTA_E_ARG.  Neither touches the
+ * env records, and muavta_set of this field does not wait for the handle's streams unless a policy is installed. */
+
 /* MLP-ContextPair: ContextPairHybrid(use_attention=False) (TaskAllocation/Hybrid/ContextPairHybrid.py:154-210,213-240).  It inherits
  * PairCostHybrid.plan — the tokens, edge_valid, the scored Hungarian and the gate are MUAVTA_ALLOC_MLP_PAIR's — and differs in the
  * network: pair_mlp = Linear(K, 192) - ReLU - Linear(192, 192) - ReLU - Linear(192, 1) over
@@ -297,7 +325,7 @@ int muavta_pair_scores_device(MuavtaEnv* env, float* scores, float* logits);
  * a_pool / t_pool: the masked means of the agent / task token rows, context: build_context_summary (muavta_context).  There is NO
  * allocator number of its own: MUAVTA_ALLOC_MLP_PAIR runs the installed learned pair policy, and the handle holds ONE policy —
  * muavta_set_pair_policy and muavta_set_context_pair_policy each replace whatever is installed, of either kind; the kind selects the
- * kernel instantiation.  muavta_pair_scores(_device) serve both kinds with the same [N, 16, 32] outputs (an MLP-Coalition: [N, 16, 48]); muavta_rollout_record refuses
+ * kernel instantiation.  muavta_pair_scores(_device) serve both kinds with the same [N, 16, 32] outputs (wide token pads: [N, 48, 64]; an MLP-Coalition: [N, 16, 48]); muavta_rollout_record refuses
  * the mode as before.  Semantics of the call as muavta_set_pair_policy: the weights (HOST pointers, state_dict layout, w0 [192, K] with
  * the reference's column order) are copied, the call is ordered behind every launch queued on both state lanes and synchronises; if a
  * lane cannot take the weights the previous policy is put back; a second lane created later gets its copy; NULL clears the policy

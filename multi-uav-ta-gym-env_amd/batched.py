@@ -20,7 +20,7 @@ F = {name: i for i, name in enumerate([
     "AGENT_POS", "AGENT_STATE", "AGENT_HEAD", "AGENT_QUEUE", "AGENT_NFT", "AGENT_NFP", "AGENT_CAPS", "AGENT_ATTACK_CAP",
     "AGENT_TYPE", "AGENT_NAME_IDX", "AGENT_DIST", "AGENT_MISC", "TASK_ID", "TASK_STATUS", "TASK_POS", "TASK_CUR",
     "TASK_ALLOC", "TASK_ORG_DONE", "TASK_META", "TASK_TIMES", "KNOWN", "THREAT_POS", "THREAT_META", "SCALARS",
-    "OPEN_IDS", "EVENTS", "EVENT_LIST", "STAGED_ACTIONS", "ERROR", "RELEASE_LOG", "KNOWN_COUNT", "ESCORTS"])}
+    "OPEN_IDS", "EVENTS", "EVENT_LIST", "STAGED_ACTIONS", "ERROR", "RELEASE_LOG", "KNOWN_COUNT", "ESCORTS", "TOKEN_PADS"])}
 
 
 class PolicyKind(NamedTuple):
@@ -30,7 +30,7 @@ class PolicyKind(NamedTuple):
     label: str               # in messages
     hidden: int
     cols: dict               # raw_features as the C struct takes it -> columns of pair_mlp.0.weight
-    max_tasks: int           # the grid of pair_scores is 16 x max_tasks
+    max_tasks: int           # the grid of pair_scores is 16 x max_tasks (a kind that follows the token pads: 48 x 64 while the wide pads are set)
     struct: str              # native.<struct>, the argument of libmuavta's <setter>
     setter: str
     alias: Optional[str]     # the set_allocator name that runs this kind only ('mlp_pair' runs whichever is installed)
@@ -90,6 +90,7 @@ class BatchedMultiUAVEnv:
         self.possible_agents = self.params.possible_agents
         self._alloc_mode = 0
         self._pair_policy = None   # what set_pair_policy last installed (parse_pair_policy's dict)
+        self._token_pads = self.TOKEN_PADS[0]  # set_token_pads
         self.escalated = {}     # rollout(escalate=True): env index -> (handle of the larger tile, row)
         self._esc_rows = None
 
@@ -191,18 +192,21 @@ class BatchedMultiUAVEnv:
                 raise ValueError(f"set_pair_policy: {src!r} is not a checkpoint of tensors and plain values (torch.load(weights_only=True): {exc}); "
                                  "load it yourself and pass the state_dict") from exc
             return cls._policy_source(src)
-        meta = {"raw": None, "clamp": None, "ck_kind": None, "use_attention": False, "escort": None, "saved": True}
+        meta = {"raw": None, "clamp": None, "ck_kind": None, "use_attention": False, "escort": None, "saved": True, "pads": None}
         if hasattr(src, "net") and hasattr(src, "use_attention"):  # the hybrid itself: read as the checkpoint its .save writes
             if hasattr(src, "commit_threshold") and not hasattr(src, "raw_features"):  # an AttentionEscort
                 own = {"version": 2, "max_tasks": int(src.max_tasks), "max_agents": int(src.max_agents)}
             else:  # a PairCostHybrid / ContextPairHybrid
-                own = {"kind": getattr(src, "kind", None), "raw_features": src.raw_features, "score_clamp": src.score_clamp}
+                own = {"kind": getattr(src, "kind", None), "raw_features": src.raw_features, "score_clamp": src.score_clamp,
+                       "max_tasks": getattr(src, "max_tasks", None), "max_agents": getattr(src, "max_agents", None)}
             src, meta["saved"] = {"state_dict": src.net.state_dict(), "use_attention": bool(src.use_attention), **own}, False
         if hasattr(src, "keys") and "state_dict" in src.keys():  # what PairCostHybrid.save (PairCostHybrid.py:469-485) or AttentionEscort.save writes
             escort = "version" in src.keys() and "raw_features" not in src.keys()
             meta.update(use_attention=bool(src.get("use_attention", escort)), ck_kind=src.get("kind"), raw=bool(src.get("raw_features", False)))
             if escort:
                 meta["escort"] = {key: src.get(key) for key in ("version", "max_tasks", "max_agents")}
+            elif src.get("max_tasks") is not None and src.get("max_agents") is not None:  # the token pads the hybrid was built with (PairCostHybrid.py:469-485)
+                meta["pads"] = (int(src["max_tasks"]), int(src["max_agents"]))
             if "score_clamp" in src.keys():
                 meta["clamp"] = float(src["score_clamp"])
             return src["state_dict"], meta
@@ -248,7 +252,9 @@ class BatchedMultiUAVEnv:
     @classmethod
     def parse_pair_policy(cls, src, score_clamp: Optional[float] = None):
         """The learned policy network of `src` as {'w0','b0','w1','b1','w2','b2': C-contiguous float32 arrays in state_dict layout,
-        'raw_features': what the C struct takes, 'score_clamp': float, 'hidden': int, 'kind': a key of `POLICY_KINDS`}.  `src`: a path to a
+        'raw_features': what the C struct takes, 'score_clamp': float, 'hidden': int, 'kind': a key of `POLICY_KINDS`, 'pads': the
+        (max_tasks, max_agents) a saved checkpoint or the hybrid object was built with — one of `TOKEN_PADS`, anything else is refused —
+        or None for a bare mapping, which carries none}.  `src`: a path to a
         checkpoint the reference's .save wrote (torch is imported only then), a loaded checkpoint (a mapping with a 'state_dict' entry), a
         state_dict-like mapping with pair_mlp.{0,2,4}.{weight,bias} (torch tensors or arrays; an optional 'raw_features' / 'score_clamp'
         entry is honoured), or the hybrid object itself.  `POLICY_KINDS` lists the kinds with their hidden size and layer 1's columns, by
@@ -270,17 +276,30 @@ class BatchedMultiUAVEnv:
         # (a net with two faults keeps the message it always had: an MLP-Coalition was asked for its width first, the others for their shapes)
         for check in (width, shapes) if kind.name == "coalition" else (shapes, width):
             check()
+        if meta["pads"] is not None and meta["pads"] not in cls.TOKEN_PADS:
+            raise ValueError(f"set_pair_policy: the policy was built with max_tasks = {meta['pads'][0]}, max_agents = {meta['pads'][1]}; the device runs the "
+                             "token pads (max_tasks, max_agents) = (32, 16) and (64, 48) only")
         clamp = float(score_clamp) if score_clamp is not None else meta["clamp"]
         if clamp is None:
             clamp = 0.35  # SCORE_CLAMP (PairCostHybrid.py): the value every checkpoint of the reference is trained and saved with
         return {**dict(zip(cls._W, arrays)), "raw_features": next(r for r, c in kind.cols.items() if c == cols), "score_clamp": clamp,
-                "hidden": hidden, "kind": kind.name}
+                "hidden": hidden, "kind": kind.name, "pads": meta["pads"]}
 
     def set_pair_policy(self, src, score_clamp: Optional[float] = None):
         """muavta_set_pair_policy / muavta_set_context_pair_policy: the network `set_allocator('mlp_pair')` and `pair_scores` run (see
         `parse_pair_policy` for `src`; None clears it).  The weights are copied; a second call replaces them — of any kind —
-        also between rollouts."""
-        self._install_policy(None if src is None else self.parse_pair_policy(src, score_clamp))
+        also between rollouts.  A saved checkpoint or a hybrid object names the token pads it was built with: `set_token_pads` is called
+        with them first ((64, 48) on a 16-agent tile: ValueError, and the installed policy stays); a bare state_dict mapping carries
+        none and leaves the setting alone."""
+        pol = None if src is None else self.parse_pair_policy(src, score_clamp)
+        before = self.token_pads
+        if pol is not None and pol["pads"] is not None:
+            self.set_token_pads(*pol["pads"])
+        try:
+            self._install_policy(pol)
+        except MuavtaError:
+            self.set_token_pads(*before)  # (the previous policy is kept by the library: so are the pads it ran with)
+            raise
 
     def _install_policy(self, pol: Optional[dict]):
         """what `parse_pair_policy` returned, through its kind's setter"""
@@ -292,11 +311,35 @@ class BatchedMultiUAVEnv:
             self._ck(getattr(self.L, kind.setter)(self.h, C.byref(spec)))
         self._pair_policy = pol
 
+    TOKEN_PADS = ((32, 16), (64, 48))  # (max_tasks, max_agents): PairCostHybrid.py:26-27, experiments/wps_eval.py:422-434
+
+    def set_token_pads(self, max_tasks: int = 32, max_agents: int = 16):
+        """muavta_set(MUAVTA_F_TOKEN_PADS): the (max_tasks, max_agents) that 'urgency_pair' and 'mlp_pair' with an MLP-Pair or MLP-ContextPair
+        policy plan over — (32, 16), the default, or (64, 48), the pads of the reference's scaled suites (WPS_attn_L / _XL / _OS18 /
+        _OS24).  Every path of those modes follows it (rollout, allocate / step_staged, parts, both lanes, escalation) and so does the
+        shape of `pair_scores`.  MLP-Coalition and 'urgency_coalition' are not affected.  ValueError for any other pair, and for the
+        wide pads on a tile with 16 agent rows, whose kernels keep the narrow pads: build such a case on the 24 x 48 tile."""
+        pads = (int(max_tasks), int(max_agents))
+        if pads not in self.TOKEN_PADS:
+            raise ValueError(f"set_token_pads: (max_tasks, max_agents) = {pads}; the supported token pads are (32, 16) and (64, 48)")
+        if pads != self.TOKEN_PADS[0] and self.A_tile <= 16:
+            raise ValueError(f"set_token_pads: the {self.A_tile} x {self.T} tile keeps the (32, 16) pads; for (64, 48) build the handle on the 24 x 48 tile: "
+                             "params_for_case(case, tile_agents=24, tile_tasks=48, tile_threats=24)")
+        v = np.array(pads, dtype=np.int32)
+        self._ck(self.L.muavta_set(self.h, F["TOKEN_PADS"], _vp(v), v.nbytes))
+        self._token_pads = pads
+
+    @property
+    def token_pads(self):
+        """(max_tasks, max_agents) of `set_token_pads`"""
+        return self._token_pads
+
     def pair_scores(self, out=None, want_logits: bool = False):
-        """muavta_pair_scores: the policy's scores (and logits) f32 [N, 16, 32] ([N, 16, 48] while the recorded policy is an
-        MLP-Coalition) of every env's current state, 0 where edge_valid is 0.  numpy by default (synchronises); `out` = {'scores': t[, 'logits': t]} of contiguous CUDA torch tensors goes through
+        """muavta_pair_scores: the policy's scores (and logits) f32 [N, 16, 32] ([N, 48, 64] while the wide token pads are set; [N, 16, 48] while the recorded policy is an
+        MLP-Coalition, whatever the pads) of every env's current state, 0 where edge_valid is 0.  numpy by default (synchronises); `out` = {'scores': t[, 'logits': t]} of contiguous CUDA torch tensors goes through
         the device entry on the handle's stream without a sync and is returned."""
-        shape = (self.n_envs, 16, (self._policy_kind() or POLICY_KINDS["pair"]).max_tasks)
+        kind = self._policy_kind() or POLICY_KINDS["pair"]
+        shape = (self.n_envs, 16, kind.max_tasks) if kind.name == "coalition" or self.token_pads == self.TOKEN_PADS[0] else (self.n_envs, self.token_pads[1], self.token_pads[0])
         if out is not None:
             if not out:
                 raise ValueError("pair_scores: out must hold a 'scores' and / or a 'logits' tensor")
@@ -606,6 +649,8 @@ class BatchedMultiUAVEnv:
                 p.tile_agents, p.tile_tasks, p.tile_threats = a, t, max(hh, self.H)
                 h = BatchedMultiUAVEnv(p, max(len(idx), 64), device=self.device_index)
                 self._esc_handles[rung] = h
+            if h.token_pads != self.token_pads:  # (every rung above the 16-agent tiles takes either pads)
+                h.set_token_pads(*self.token_pads)
             if self._pair_policy is not None and h._pair_policy is not self._pair_policy:  # (new handle, or the policy changed since)
                 h._install_policy(self._pair_policy)
             h._ck(h.L.muavta_set_allocator(h.h, self._alloc_mode))
@@ -850,6 +895,7 @@ class BatchedMultiUAVEnv:
             "OPEN_IDS": ((N, T), i32), "EVENTS": ((N, E, 2), i32), "EVENT_LIST": ((N, E, 2), i32),
             "STAGED_ACTIONS": ((N, self.A_tile, 3), i32), "ERROR": ((N,), i32),
             "RELEASE_LOG": ((N, 1 + 29 * T), f64), "KNOWN_COUNT": ((N, A), i32), "ESCORTS": ((N, self.A_tile, 2), i32),
+            "TOKEN_PADS": ((2,), i32),  # (a setting of the handle: set_token_pads / token_pads)
         }
         return self._shapes[name]
 

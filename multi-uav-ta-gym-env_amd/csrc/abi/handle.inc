@@ -50,6 +50,7 @@ struct MuavtaEnv {
   MuavtaParams params;
   int tile = TK16;
   int alloc_mode = 0;  // MUAVTA_ALLOC_*
+  int pad_t = 32, pad_a = 16;  // MUAVTA_F_TOKEN_PADS (PairCostHybrid.py:26-27: DEFAULT_MAX_TASKS / DEFAULT_MAX_AGENTS); the same on both lanes
   DevBuf<void> d_tok;  // muavta_tokens staging (host-buffer variant)
   DevBuf<double> d_rel;  // release log [N, 1 + MUAVTA_REL_ROW*T] (muavta_set_release_log)
   // Seeding pipeline: seeds upload + k_seed go into one of two slots, so that the seeding of launch i+1 overlaps launch i (k_seed uses
@@ -84,6 +85,7 @@ struct MuavtaEnv {
   DevBuf<double> d_metrics;
   DevBuf<float> d_pol_w, d_pol_scratch;  // muavta_set_pair_policy: this lane's copy of the packed weights, its per-env token / score scratch
   DevBuf<float> d_pol_scratch_e;         // ... and the larger one of the MLP-Coalition kind ([N][PolCoalition::FLOATS]), allocated when such a policy first reaches the lane
+  DevBuf<float> d_pol_scratch_w;         // ... and the one of MLP-Pair / MLP-ContextPair at the wide token pads ([N][PolContextPairWide::FLOATS]), allocated when wide pads first meet such a policy on the lane
   int pol_kind = POL_PAIR;               // ... and which network they hold (push_policy): selects the kernel instantiation of MUAVTA_ALLOC_MLP_PAIR on this lane
   ObsPtrs O{};  // the observation buffers as the kernels see them: views of obs_mem
   DevBuf<void> obs_mem[7];
@@ -144,6 +146,7 @@ extern "C" int muavta_create(const MuavtaParams* params, int32_t n_envs, int32_t
 extern "C" int muavta_destroy(MuavtaEnv* e);
 extern "C" int muavta_set_slot_cap(MuavtaEnv* e, int32_t cap);
 static int push_policy(MuavtaEnv* lane, const MuavtaEnv::HandleLevel& hl);
+static int set_pads_lane(MuavtaEnv* lane, const MuavtaEnv::HandleLevel& hl, int max_tasks, int max_agents);
 static int create_lane(const MuavtaParams* params, int32_t n_envs, int32_t device, MuavtaEnv* owner, MuavtaEnv** out);
 
 namespace {
@@ -153,22 +156,31 @@ namespace {
 // Where a kernel template is first named decides where the compiler emits the kernel, and that order is kept (it is why the mapping tests
 // the kinds from the last to the first, and why it returns `auto`: a function with a deduced return type is instantiated where it is
 // first called, so the kernels named through it stay where the hand-written selections it replaces had them).
+// wide: the lane's token pads are the 64 x 48 ones (MUAVTA_F_TOKEN_PADS) — MLP-Pair and MLP-ContextPair then run their wide traits; MLP-Coalition
+// keeps its own 16 x 48 escort grid.  The wide traits exist on the tiles with more than 16 agent rows only (runs_on): the setter refuses wide
+// pads elsewhere, and a launch site that dispatches over the tiles names no wide kernel of a 16-agent tile.
 template <class F>
-auto with_policy(int kind, F f) {
+auto with_policy(int kind, bool wide, F f) {
   switch (kind) {
     case POL_COALITION: return f(PolCoalition{});
-    case POL_CONTEXT_PAIR: return f(PolContextPair{});
-    default: return f(PolPair{});
+    case POL_CONTEXT_PAIR: return !wide ? f(PolContextPair{}) : f(PolContextPairWide{});
+    default: return !wide ? f(PolPair{}) : f(PolPairWide{});
   }
 }
+template <class TL, class TAG>
+constexpr bool runs_on() { return !TAG::WIDE || TL::A > 16; }
+static bool wide_pads(const MuavtaEnv* e) { return e->pad_t == 64; }
 template <class F>
 auto with_allocator(const MuavtaEnv* e, F f) {
-  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) return with_policy(e->pol_kind, [&](auto pol) { return f(AllocLearned<decltype(pol)>{}); });
+  if (e->alloc_mode == MUAVTA_ALLOC_MLP_PAIR) return with_policy(e->pol_kind, wide_pads(e), [&](auto pol) { return f(AllocLearned<decltype(pol)>{}); });
   if (e->alloc_mode >= MUAVTA_ALLOC_CAP_GREEDY) return f(AllocBaseline{});
+  if (e->alloc_mode == MUAVTA_ALLOC_URGENCY_PAIR && wide_pads(e)) return f(AllocUrgencyWide{});
   return f(AllocHungarian{});
 }
 template <class F>
 void for_each_policy(F f) { f(PolPair{}); f(PolContextPair{}); f(PolCoalition{}); }
+template <class F>
+void for_each_wide_policy(F f) { f(PolPairWide{}); f(PolContextPairWide{}); }
 
 // Tiles whose LDS image exceeds the default limit: every kernel launched with dynamic LDS is allowed the tile's bytes, plus what its
 // allocator tag needs behind the tile.  (Named in the order the kernels are emitted in, see above.)
@@ -183,8 +195,13 @@ int launch_attr(MuavtaEnv* e) {
   allocator(AllocHungarian{});
   allow(&k_rollout<TL, true, AllocHungarian>, 0); allow(&k_metrics<TL>, 0); allow(&k_observe<TL>, 0); allow(&k_tokens<TL>, 0); allow(&k_call<TL>, 0); allow(&k_context<TL>, 0);
   allocator(AllocBaseline{});
-  for_each_policy([&](auto pol) { allow(&k_pair_scores<TL, decltype(pol)>, 0); allocator(AllocLearned<decltype(pol)>{}); });
+  const auto policy = [&](auto pol) { allow(&k_pair_scores<TL, decltype(pol)>, 0); allocator(AllocLearned<decltype(pol)>{}); };
+  for_each_policy(policy);
   allow(&k_allocate_scored<TL>, SCORED_EXTRA_LDS);
+  if constexpr (TL::A > 16) {
+    for_each_wide_policy(policy);
+    allocator(AllocUrgencyWide{}); allow(&k_rollout<TL, true, AllocUrgencyWide>, 0);
+  }
   if (lds > 48 * 1024)
     for (const auto& k : ks) HIPCHK(e, hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + k.second)));
   return MUAVTA_OK;
@@ -285,6 +302,7 @@ static int ensure_twin(MuavtaEnv* e) {  // create the second lane (same configur
   if (rc == MUAVTA_OK && e->n_parts) rc = muavta_set_parts(t, e->n_parts);
   if (rc == MUAVTA_OK && e->d_rel) rc = muavta_set_release_log(t, 1);
   if (rc == MUAVTA_OK) t->alloc_mode = e->alloc_mode;
+  if (rc == MUAVTA_OK && set_pads_lane(t, MuavtaEnv::HandleLevel{}, e->pad_t, e->pad_a) != MUAVTA_OK) { e->err = t->err; rc = MUAVTA_E_HIP; }
   if (rc == MUAVTA_OK && e->hl.pol_set && push_policy(t, e->hl) != MUAVTA_OK) { e->err = t->err; rc = MUAVTA_E_HIP; }
   if (rc == MUAVTA_OK && e->P.slot_cap && muavta_set_slot_cap(t, e->P.slot_cap) != MUAVTA_OK) rc = MUAVTA_E_HIP;
   // the waits the caller queued before this lane existed hold for it too (its part streams fork from its main stream at their first launch)
@@ -701,6 +719,38 @@ int muavta_set_slot_cap(MuavtaEnv* e, int32_t cap) {  // test hook: an env may u
   e->P.slot_cap = (cap > 0 && cap < e->T) ? cap : 0;
   HIPCHK(e, hipMemcpy((char*)e->d_ctx.p + offsetof(DevCtx, P) + offsetof(DevParams, slot_cap), &e->P.slot_cap, sizeof(int32_t), hipMemcpyHostToDevice));
   return MUAVTA_OK;
+}
+// The token pads of the pair-cost planners (UrgencyPair(max_tasks, max_agents), PairCostHybrid.py:523-525; experiments/wps_eval.py:422-434).
+// Both lanes.  Every launch already queued on the handle keeps the kernels it was launched with; every later one, whatever stream it runs
+// on, is launched with the new pads' instantiations.
+static int set_pads_lane(MuavtaEnv* l, const MuavtaEnv::HandleLevel& hl, int max_tasks, int max_agents) {
+  // The pads select kernel instantiations at launch time (with_allocator, with_policy): what is already queued keeps the ones it was launched
+  // with.  Only the installed policy's scratch block is device state: push_policy rewrites it behind everything the lane still runs.
+  // An MLP-Coalition keeps its own grid and block whatever the pads: nothing of it is touched.
+  l->pad_t = max_tasks; l->pad_a = max_agents;
+  return hl.pol_set && hl.pol_kind != POL_COALITION ? push_policy(l, hl) : MUAVTA_OK;
+}
+// muavta_set(env, MUAVTA_F_TOKEN_PADS, ...)
+static int set_token_pads(MuavtaEnv* e, int32_t max_tasks, int32_t max_agents) {
+  const bool narrow = max_tasks == 32 && max_agents == 16, wide = max_tasks == 64 && max_agents == 48;
+  if (!narrow && !wide) { e->err = "muavta_set(TOKEN_PADS): (max_tasks, max_agents) is (32, 16) or (64, 48)"; return MUAVTA_E_ARG; }
+  if (wide && e->A <= 16) {
+    e->err = "muavta_set(TOKEN_PADS): the 16-agent tiles keep the 32 x 16 pads; run the case on the 24 x 48 tile for the wide ones "
+             "(params_for_case(case, tile_agents=24, tile_tasks=48, tile_threats=24))";
+    return MUAVTA_E_ARG;
+  }
+  if (e->pad_t == max_tasks && e->pad_a == max_agents) return MUAVTA_OK;  // (both lanes always hold the same pads)
+  DeviceScope scope_(e->device);
+  const int old_t = e->pad_t, old_a = e->pad_a;
+  int rc = set_pads_lane(e, e->hl, max_tasks, max_agents);
+  if (rc == MUAVTA_OK && e->hl.twin) { rc = set_pads_lane(e->hl.twin, e->hl, max_tasks, max_agents); if (rc) e->err = e->hl.twin->err; }
+  if (rc != MUAVTA_OK) {  // (out of memory for the wide scratch block: both lanes go back to the pads they had)
+    const std::string why = e->err;
+    int back = set_pads_lane(e, e->hl, old_t, old_a);
+    if (back == MUAVTA_OK && e->hl.twin) back = set_pads_lane(e->hl.twin, e->hl, old_t, old_a);
+    e->err = "muavta_set(TOKEN_PADS) failed" + std::string(back == MUAVTA_OK ? ", the previous pads are kept: " : " and the previous pads could not be restored: ") + why;
+  }
+  return rc;
 }
 int muavta_set_lanes(MuavtaEnv* e, int32_t lanes) {
   if (!e || lanes < 0 || lanes > 2) { if (e) e->err = "muavta_set_lanes: 0 (second lane on demand), 1 (one lane) or 2 (always alternate)"; return MUAVTA_E_ARG; }

@@ -85,8 +85,12 @@ static void launch_rollout(MuavtaEnv* e, const Target& t, const uint64_t* ds, in
     slot += MuavtaEnv::REC_SLOT;  // slot 1: the RecordPtrs of this launch
     hipLaunchKernelGGL(k_store_rec, dim3(1), dim3(64), 0, t.stream, blob, (uint32_t*)slot);
   }
-  const RolloutFn<TL> fn = rec ? &k_rollout<TL, true, AllocHungarian>  // (muavta_rollout_record refuses the modes past the Hungarian family)
-                               : with_allocator(e, [](auto al) -> RolloutFn<TL> { return &k_rollout<TL, false, decltype(al)>; });
+  RolloutFn<TL> rec_fn = &k_rollout<TL, true, AllocHungarian>;  // (muavta_rollout_record refuses the modes past the Hungarian family)
+  if constexpr (runs_on<TL, AllocUrgencyWide>()) { if (e->alloc_mode == MUAVTA_ALLOC_URGENCY_PAIR && wide_pads(e)) rec_fn = &k_rollout<TL, true, AllocUrgencyWide>; }
+  const RolloutFn<TL> fn = rec ? rec_fn
+                               : with_allocator(e, [](auto al) -> RolloutFn<TL> {
+                                   if constexpr (runs_on<TL, decltype(al)>()) return &k_rollout<TL, false, decltype(al)>; else return nullptr;  // (wide pads are refused on the 16-agent tiles)
+                                 });
   hipLaunchKernelGGL(fn, dim3(t.count), dim3(WG), extra_lds, t.stream, (const DevCtx*)e->d_ctx, ds, n_steps, interval, use_vis, e->alloc_mode, write_obs,
                      (double*)e->d_metrics, sb, (const RecordPtrs<TL>*)slot, epoch, t.first);
 }
@@ -204,7 +208,7 @@ int muavta_step_part(MuavtaEnv* e, int32_t part, const int32_t* act_agent, const
 static AllocateKernel allocate_kernel(MuavtaEnv* e) {
   return with_allocator(e, [e](auto al) {
     AllocateKernel k{};
-    DISPATCH(e, (k = AllocateKernel{&k_allocate<TL, decltype(al)>, Lds<TL>::bytes() + al.EXTRA_LDS}));
+    DISPATCH(e, if constexpr ((runs_on<TL, decltype(al)>())) (k = AllocateKernel{&k_allocate<TL, decltype(al)>, Lds<TL>::bytes() + al.EXTRA_LDS}));
     return k;
   });
 }

@@ -271,9 +271,16 @@ static int push_policy(MuavtaEnv* l, const MuavtaEnv::HandleLevel& hl) {
       HIPCHK(l, l->d_pol_scratch_e.alloc((size_t)l->n_envs * se_floats * sizeof(float)));
       HIPCHK(l, hipMemsetAsync(l->d_pol_scratch_e, 0, (size_t)l->n_envs * se_floats * sizeof(float), l->stream));
     }
+    const bool wide = hl.pol_kind != POL_COALITION && wide_pads(l);
+    if (wide && !l->d_pol_scratch_w) {  // the 48 x 64 block: only lanes on which wide pads meet an MLP-Pair / MLP-ContextPair pay for it
+      const size_t sw_floats = PolContextPairWide::FLOATS;
+      static_assert(PolContextPairWide::FLOATS >= PolPairWide::FLOATS, "buffer sizes");
+      HIPCHK(l, l->d_pol_scratch_w.alloc((size_t)l->n_envs * sw_floats * sizeof(float)));
+      HIPCHK(l, hipMemsetAsync(l->d_pol_scratch_w, 0, (size_t)l->n_envs * sw_floats * sizeof(float), l->stream));
+    }
     if (hl.pol_w.size() > w_floats) { l->err = "push_policy: packed weights larger than the lane's buffer"; return MUAVTA_E_ARG; }
     HIPCHK(l, hipMemcpyAsync(l->d_pol_w, hl.pol_w.data(), hl.pol_w.size() * sizeof(float), hipMemcpyHostToDevice, l->stream));
-    pd.w = l->d_pol_w; pd.scratch = hl.pol_kind == POL_COALITION ? l->d_pol_scratch_e : l->d_pol_scratch; pd.raw = hl.pol_raw; pd.clamp = hl.pol_clamp; pd.kind = hl.pol_kind;
+    pd.w = l->d_pol_w; pd.scratch = hl.pol_kind == POL_COALITION ? l->d_pol_scratch_e : wide ? l->d_pol_scratch_w : l->d_pol_scratch; pd.raw = hl.pol_raw; pd.clamp = hl.pol_clamp; pd.kind = hl.pol_kind;
   }
   HIPCHK(l, hipMemcpyAsync((char*)l->d_ctx.p + offsetof(DevCtx, pol), &pd, sizeof(pd), hipMemcpyHostToDevice, l->stream));
   HIPCHK(l, hipStreamSynchronize(l->stream));  // `pd` is a stack object
@@ -381,8 +388,9 @@ int muavta_pair_scores_device(MuavtaEnv* e, float* scores, float* logits) {
   if (!scores && !logits) return MUAVTA_OK;
   DeviceScope scope_(e->device);
   MAIN_OP(e);
-  with_policy(e->pol_kind, [&](auto pol) {
-    DISPATCH(e, hipLaunchKernelGGL((k_pair_scores<TL, decltype(pol)>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits));
+  with_policy(e->pol_kind, wide_pads(e), [&](auto pol) {
+    DISPATCH(e, if constexpr ((runs_on<TL, decltype(pol)>()))
+                    hipLaunchKernelGGL((k_pair_scores<TL, decltype(pol)>), dim3(e->n_envs), dim3(WG), Lds<TL>::bytes(), e->stream, (const DevCtx*)e->d_ctx, scores, logits));
   });
   HIPCHK(e, hipGetLastError());
   return MUAVTA_OK;
@@ -392,7 +400,7 @@ int muavta_pair_scores(MuavtaEnv* e, float* scores, float* logits) {
   if (!e->hl.pol_set) { e->err = "muavta_pair_scores: no policy (muavta_set_pair_policy first)"; return MUAVTA_E_STATE; }
   if (!e->did_reset) { e->err = "muavta_pair_scores before reset"; return MUAVTA_E_STATE; }
   DeviceScope scope_(e->device);
-  const size_t one = with_policy(e->pol_kind, [e](auto pol) { typedef typename decltype(pol)::Blk B; return (size_t)e->n_envs * B::MA * B::MT * sizeof(float); });  // [N, 16, 32], MLP-Coalition: [N, 16, 48]
+  const size_t one = with_policy(e->pol_kind, wide_pads(e), [e](auto pol) { typedef typename decltype(pol)::Blk B; return (size_t)e->n_envs * B::MA * B::MT * sizeof(float); });  // [N, 16, 32] (wide pads: [N, 48, 64]), MLP-Coalition: [N, 16, 48]
   if (int rc = grow_staging(e, 2 * one)) return rc;  // (shares the staging buffer of muavta_tokens' host variant)
   float* ds = (float*)e->d_tok.p;
   float* dl = (float*)((char*)e->d_tok.p + one);
@@ -554,6 +562,12 @@ int muavta_metrics(MuavtaEnv* e, double* out) {
 
 int muavta_get(MuavtaEnv* e, MuavtaField field, void* dst, size_t bytes) {
   if (!e || !dst) return MUAVTA_E_ARG;
+  if (field == MUAVTA_F_TOKEN_PADS) {  // a setting of the handle: no env record is read
+    if (bytes != 2 * sizeof(int32_t)) { e->err = "muavta_get(TOKEN_PADS): i32 [2], 8 bytes"; return MUAVTA_E_ARG; }
+    const int32_t pads[2] = {e->pad_t, e->pad_a};
+    memcpy(dst, pads, sizeof(pads));
+    return MUAVTA_OK;
+  }
   DeviceScope scope_(e->device);
   if (field == MUAVTA_F_RELEASE_LOG) {
     const size_t want = (size_t)e->n_envs * (1 + MUAVTA_REL_ROW * e->T) * sizeof(double);
@@ -572,6 +586,12 @@ int muavta_get(MuavtaEnv* e, MuavtaField field, void* dst, size_t bytes) {
 
 int muavta_set(MuavtaEnv* e, MuavtaField field, const void* src, size_t bytes) {
   if (!e || !src) return MUAVTA_E_ARG;
+  if (field == MUAVTA_F_TOKEN_PADS) {  // a setting of the handle: no env record is written
+    if (bytes != 2 * sizeof(int32_t)) { e->err = "muavta_set(TOKEN_PADS): i32 [2], 8 bytes"; return MUAVTA_E_ARG; }
+    int32_t pads[2];
+    memcpy(pads, src, sizeof(pads));
+    return set_token_pads(e, pads[0], pads[1]);
+  }
   DeviceScope scope_(e->device);
   int rc = sync_host(e);
   if (rc) return rc;

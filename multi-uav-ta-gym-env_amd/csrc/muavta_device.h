@@ -151,11 +151,12 @@ struct PackedMlp {
   enum { HID = HID_, W0_ROWS = W0_ROWS_,
          W0 = 0, B0 = W0 + HID * W0_ROWS, W1 = B0 + HID, B1 = W1 + HID * HID, W2 = B1 + HID, B2 = W2 + HID, FLOATS = B2 + 16 };
 };
-// The front of a policy's per-env scratch block, in floats: the token tensors of the plan being made — MT task rows of DT features, 16
+// The front of a policy's per-env scratch block, in floats: the token tensors of the plan being made — MT task rows of DT features, MA
 // agent rows of DA — and its scores.  END: the first float behind the pad masks; what follows belongs to the policy's traits.
-template <int MT_, int DT, int DA>
+template <int MT_, int DT, int DA, int MA_ = 16>
 struct TokenBlock {
-  enum { MA = 16, MT = MT_,
+  static_assert(MT_ % 4 == 0 && MA_ % 4 == 0, "the pad masks are bytes packed into whole floats");
+  enum { MA = MA_, MT = MT_,
          TF = 0, AF = TF + MT * DT, EV = AF + MA * DA, SCORES = EV + MA * MT, TID = SCORES + MA * MT,
          AID = TID + MT, TMASK = AID + MA, AMASK = TMASK + MT / 4, END = AMASK + MA / 4 };
 };
@@ -168,12 +169,13 @@ struct TokenBlock {
 //   SIGMOID             score = sigmoid of the logit clipped to +-20 (and pad pairs are masked) instead of tanhf(logit) * clamp
 //   GATE, FLAGS, FILL   its plan's MUAVTA_GATE_* and MUAVTA_SC_* flags, and whether that plan reads masked cells (they are written as 0)
 //   MAX_WAVES           waves per SIMD its rollout instantiation is built for: the hidden activations live in registers
+//   WIDE                the variant over the 48 x 64 token pads (MUAVTA_F_TOKEN_PADS): instantiated for the tiles with more than 16 agent rows only
 // MLP-Pair (muavta_set_pair_policy): Linear(25|20, 128) - ReLU - Linear(128, 128) - ReLU - Linear(128, 1) over build_pair_tokens(env, 32, 16).
 struct PolPair {
   typedef PackedMlp<128, 25> W;
   typedef TokenBlock<32, 13, 12> Blk;
   enum { KIND = POL_PAIR, FLOATS = (Blk::END + 3) & ~3, RAW_TOKENS = 1, LIST_IN_BLOCK = 0, SIGMOID = 0,
-         GATE = MUAVTA_GATE_TRAINER, FLAGS = MUAVTA_SC_EDGE_VALID_ONLY, FILL = 0, MAX_WAVES = 3 };
+         GATE = MUAVTA_GATE_TRAINER, FLAGS = MUAVTA_SC_EDGE_VALID_ONLY, FILL = 0, MAX_WAVES = 3, WIDE = 0 };
   static constexpr int tok_kind(int raw) { return raw ? MUAVTA_TOK_PAIR_RAW : MUAVTA_TOK_PAIR; }
   static constexpr int da(bool raw) { return raw ? 11 : 12; }
   static constexpr int dt(bool raw) { return raw ? 9 : 13; }
@@ -196,12 +198,28 @@ struct PolCoalition {
   typedef PackedMlp<256, 38> W;
   typedef TokenBlock<48, 22, 16> Blk;
   enum { KIND = POL_COALITION, LIST = Blk::END, FLOATS = (LIST + Blk::MA * Blk::MT / 2 + 3) & ~3, RAW_TOKENS = 0, LIST_IN_BLOCK = 1, SIGMOID = 1,
-         GATE = MUAVTA_GATE_ESCORT, FLAGS = MUAVTA_SC_COMMIT, FILL = 1, MAX_WAVES = 1 };
+         GATE = MUAVTA_GATE_ESCORT, FLAGS = MUAVTA_SC_COMMIT, FILL = 1, MAX_WAVES = 1, WIDE = 0 };
   static constexpr int tok_kind(int) { return MUAVTA_TOK_ESCORT; }
   static constexpr int da(bool) { return 16; }
   static constexpr int dt(bool) { return 22; }
   static constexpr int np(bool) { return 0; }
 };
+// MLP-Pair / MLP-ContextPair over build_pair_tokens(env, 64, 48[, raw]): PairCostHybrid(max_tasks=64, max_agents=48) and the matching ContextPair
+// hybrid of the reference's scaled suites (experiments/wps_eval.py:422-434).  The same networks, packed weights, feature widths, gate and flags —
+// an MLP's weights do not depend on the pads — over a 48 x 64 grid.  The scratch block: the token block of that grid, then the list of valid
+// cells (3,072 x u16: more than the idle LDS in front of Scratch::resid holds, so it sits in the block as MLP-Coalition's does), then for
+// MLP-ContextPair PRE and HEAD as in the narrow block.  A buffer of its own, allocated when wide pads first meet an installed policy.
+struct PolPairWide : PolPair {
+  typedef TokenBlock<64, 13, 12, 48> Blk;
+  enum { LIST = Blk::END, FLOATS = (LIST + Blk::MA * Blk::MT / 2 + 3) & ~3, LIST_IN_BLOCK = 1, WIDE = 1 };
+};
+struct PolContextPairWide : PolPairWide {
+  typedef PackedMlp<192, 58> W;
+  enum { KIND = POL_CONTEXT_PAIR, PRE = PolPairWide::FLOATS, HEAD = PRE + 36, FLOATS = HEAD + W::HID, MAX_WAVES = 2 };
+  static constexpr int np(bool raw) { return da(raw) + dt(raw) + (raw ? 1 : 8); }
+};
+static_assert(PolPairWide::Blk::SCORES == 4480 && PolPairWide::LIST == 7692 && PolPairWide::FLOATS == 9228 && PolContextPairWide::HEAD == 9264 &&
+              PolContextPairWide::FLOATS == 9456, "wide MLP-Pair / MLP-ContextPair scratch block");
 // (the values of the PW_* / PC_* / PWE_* and PS_* / PSC_* / PE_* enums these templates replace: neither layout may move)
 static_assert(PolPair::W::FLOATS == 19984 && PolContextPair::W::FLOATS == 48592 && PolCoalition::W::FLOATS == 76048, "packed-weight layout");
 static_assert(PolPair::FLOATS == 1692 && PolPair::Blk::SCORES == 1120 && PolContextPair::PRE == 1692 && PolContextPair::HEAD == 1728 &&

@@ -296,10 +296,12 @@ static_assert(Lds<Tile16>::bytes() + SCORED_EXTRA_LDS <= 10240, "k_run / k_rl_st
 // the tile (allocate<true>'s task list) and the waves per SIMD its rollout is built for.  A fourth learned policy is a traits type next to
 // the three in muavta_device.h, whatever of sim/policy.inc's forward pass its traits cannot express, and one line each in with_policy
 // and for_each_policy (abi/handle.inc): every kernel instantiation, launch attribute and host-side size follows from there.
-struct AllocHungarian { enum { EXTRA_LDS = 0, MAX_WAVES = 8 }; };  // MUAVTA_ALLOC_HUNGARIAN .. _HUNGARIAN_GATED (sim/allocate.inc)
-struct AllocBaseline { enum { EXTRA_LDS = 0, MAX_WAVES = 8 }; };   // MUAVTA_ALLOC_CAP_GREEDY, _PI (sim/baselines.inc): the Hungarian kernels do not carry this code
+struct AllocHungarian { enum { EXTRA_LDS = 0, MAX_WAVES = 8, WIDE = 0 }; };  // MUAVTA_ALLOC_HUNGARIAN .. _HUNGARIAN_GATED (sim/allocate.inc)
+// MUAVTA_ALLOC_URGENCY_PAIR at the wide token pads (MUAVTA_F_TOKEN_PADS = (64, 48)): allocate() with PAD_T x PAD_A = 64 x 48.  The tiles with more than 16 agent rows only
+struct AllocUrgencyWide { enum { EXTRA_LDS = 0, MAX_WAVES = 8, WIDE = 1 }; };
+struct AllocBaseline { enum { EXTRA_LDS = 0, MAX_WAVES = 8, WIDE = 0 }; };   // MUAVTA_ALLOC_CAP_GREEDY, _PI (sim/baselines.inc): the Hungarian kernels do not carry this code
 template <class POL>
-struct AllocLearned { typedef POL Pol; enum { EXTRA_LDS = SCORED_EXTRA_LDS, MAX_WAVES = POL::MAX_WAVES }; };  // MUAVTA_ALLOC_MLP_PAIR (sim/policy.inc)
+struct AllocLearned { typedef POL Pol; enum { EXTRA_LDS = SCORED_EXTRA_LDS, MAX_WAVES = POL::MAX_WAVES, WIDE = POL::WIDE }; };  // MUAVTA_ALLOC_MLP_PAIR (sim/policy.inc)
 // The one place that turns a tag into the allocator's call.  sc_list: EXTRA_LDS bytes of LDS behind the tile.  A macro on purpose: as a
 // function (free or a member of Sim, both tried) the helper is one more level for the inliner, and with it the instruction streams of 24 of
 // the code object's 83 functions change (every k_rollout but the baselines', every learned k_allocate; two swapped instructions in the
@@ -307,6 +309,7 @@ struct AllocLearned { typedef POL Pol; enum { EXTRA_LDS = SCORED_EXTRA_LDS, MAX_
 #define RUN_ALLOCATOR(AL, sim, ctx, env, interval, use_vis, mode, sc_list)                                                                  \
   {                                                                                                                                        \
     if constexpr (std::is_same<AL, AllocHungarian>::value) (sim).allocate(interval, use_vis, mode);                                        \
+    else if constexpr (std::is_same<AL, AllocUrgencyWide>::value) (sim).template allocate<false, 64, 48>(interval, use_vis, mode);         \
     else if constexpr (std::is_same<AL, AllocBaseline>::value) (sim).allocate_baseline(interval, use_vis, mode);                           \
     else (sim).template allocate_learned<typename AL::Pol>(interval, use_vis, (ctx).pol, as_global((ctx).pol.scratch) + (size_t)(env) * AL::Pol::FLOATS, sc_list); \
   }
@@ -784,7 +787,7 @@ __global__ __launch_bounds__(WG) void k_tokens(const DevCtx* __restrict__ ctxp, 
 
 // muavta_pair_scores(_device): the installed policy's scores / logits of every env's CURRENT state — POL's tokens into the env's scratch
 // block, then the forward pass of sim/policy.inc, the same code the MUAVTA_ALLOC_MLP_PAIR mode runs at a replan.  scores / logits:
-// [N, 16, POL::Blk::MT] (either may be null); entries whose edge_valid is 0 are written as 0.  The env records are not changed.
+// [N, POL::Blk::MA, POL::Blk::MT] (either may be null); entries whose edge_valid is 0 are written as 0.  The env records are not changed.
 template <class TL, class POL>
 __global__ __launch_bounds__(WG) void k_pair_scores(const DevCtx* __restrict__ ctxp, float* scores, float* logits) {
   const DevCtx& ctx = ctx_ref(ctxp);
@@ -796,7 +799,7 @@ __global__ __launch_bounds__(WG) void k_pair_scores(const DevCtx* __restrict__ c
   float* scratch = as_global(ctx.pol.scratch) + (size_t)env * POL::FLOATS;
   sim.template policy_tokens<POL>(ctx.pol, scratch);
   const size_t at = (size_t)env * POL::Blk::MA * POL::Blk::MT;
-  if constexpr (POL::np(false) > 0) sim.context_prefix(ctx.pol, scratch);
+  if constexpr (POL::np(false) > 0) sim.template context_prefix<POL>(ctx.pol, scratch);
   sim.template policy_forward<POL>(ctx.pol, scratch, scores ? as_global(scores) + at : nullptr, logits ? as_global(logits) + at : nullptr, true);
 }
 

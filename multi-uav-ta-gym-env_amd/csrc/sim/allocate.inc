@@ -16,8 +16,13 @@
 
   // mode 0 (MUAVTA_ALLOC_HUNGARIAN): Local-/Global-/Coalition-Hungarian as driven by the WPS / escort harness.
   // mode 1 (MUAVTA_ALLOC_URGENCY_PAIR): TaskAllocation/Hybrid/PairCostHybrid.py:31-86,520-550 — engineered
-  //   float32 edge scores 0.5*urgency + 0.3*scarcity - 0.4*dist, clipped to +-0.35, for the first 16 live agents x
-  //   first 32 underfilled tasks, subtracted from the Hungarian cost; replan gate = experiments/wps_eval.py:64-74.
+  //   float32 edge scores 0.5*urgency + 0.3*scarcity - 0.4*dist, clipped to +-0.35, for the first PAD_A live agents x
+  //   first PAD_T underfilled tasks, subtracted from the Hungarian cost; replan gate = experiments/wps_eval.py:64-74.
+  // The token pads of UrgencyPair(max_tasks, max_agents) (MUAVTA_F_TOKEN_PADS): 32 x 16, or the 64 x 48 of the reference's scaled suites
+  //   (experiments/wps_eval.py:422-434): the template arguments PAD_T x PAD_A.  Compile-time on purpose: read from the handle's context at
+  //   run time they cost the 64-agent tile's Hungarian rollout 0.8 % (two more VGPRs, a reordered cost pass; A/B against the parent's
+  //   library, 4 alternating rounds), so the wide pads are kernel instantiations of their own (AllocUrgencyWide, muavta_kernels.hip) on the
+  //   tiles with more than 16 agent rows and every other kernel keeps the literals it always had.
   DEV int16_t* pair_info() { return T > 64 ? X.pair_info_big : X.remaining; }
   // scored template path (SC = true, muavta_allocate_scored; a template flag, not an alloc_mode value): the caller's edge scores / task priorities / reserved agents, indexed in the token layout
   //   (sc.kind, sc.MT, sc.MA) — PairCostHybrid.plan, AttentionRAH.plan, AttentionCommit / AttentionEscort._plan_from_scores
@@ -35,7 +40,7 @@
     if (gate == MUAVTA_GATE_ALLOCATOR) return (tnow - S.last_plan_step >= interval) || (S.n_dev > 0);      // should_replan (:27-41)
     return true;
   }
-  template <bool SC = false>
+  template <bool SC = false, int PAD_T = 32, int PAD_A = 16>
   DEV void allocate(int interval, int use_visibility, int mode = 0, const ScoredDev* scp = nullptr, int env = 0, uint8_t* sc_list = nullptr) {
     PROF(10);
     interval = interval < 1 ? 1 : interval;
@@ -172,8 +177,8 @@
         }
         const unsigned long long um = mode == 1 ? __ballot(under) : 0ull;
         if (k < n_plan) {
-          // (Urgency-Pair hands the allocator the 32 token rows only: tok["open_tasks"] = kept, PairCostHybrid.py:36,62)
-          const double r = (under && !(mode == 1 && n_under + prefix_count(um) >= 32)) ? residual_demand(s) : 0.0;
+          // (Urgency-Pair hands the allocator the max_tasks token rows only: tok["open_tasks"] = kept, PairCostHybrid.py:36,62)
+          const double r = (under && !(mode == 1 && n_under + prefix_count(um) >= PAD_T)) ? residual_demand(s) : 0.0;
           X.resid[s] = r;
           any_open |= r > 0;
         }
@@ -182,7 +187,7 @@
             const int rank = n_under + prefix_count(um);
             int n_know = 0;
             if (vis) for (int b = 0; b < P.n_agents; b++) n_know += (S.known[b][s >> 5] >> (s & 31)) & 1u;
-            pair_info()[s] = (rank < 32 ? rank : 255) | (n_know << 8);
+            pair_info()[s] = (rank < PAD_T ? rank : 255) | (n_know << 8);
           } else if (k < n_plan) pair_info()[s] = 255;
           n_under += __popcll(um);
         }
@@ -191,7 +196,7 @@
         const bool lv = S.a_state[lane] != -1;
         const unsigned long long lm = __ballot(lv);
         const int rk = prefix_count(lm);
-        X.live_rank[lane] = (lv && rk < 16) ? (uint8_t)rk : (uint8_t)255;
+        X.live_rank[lane] = (lv && rk < PAD_A) ? (uint8_t)rk : (uint8_t)255;
       }
       if (nr == 0 || __ballot(any_open) == 0ull) go = false;
     }
@@ -256,7 +261,7 @@
             }
             if (mode == 1) {  // urgency_edge_scores (PairCostHybrid.py:68-86) on the edges build_pair_tokens keeps (:42-60)
               const int info = pair_info()[s];
-              if ((info & 255) < 32 && X.live_rank[a] < 16 && S.a_caps[S.t_type[s]][a] > 0) {
+              if ((info & 255) < PAD_T && X.live_rank[a] < PAD_A && S.a_caps[S.t_type[s]][a] > 0) {
                 double scar = 0.0;
                 if (vis) scar = 1.0 - fmin((double)(info >> 8) / (double)n_live, 1.0);
                 double v = 0.5 * urgency + 0.3 * scar - 0.4 * div_coord(dist);
@@ -345,7 +350,7 @@
           if (vis) scar = 1.0 - fmin((double)(t.info >> 8) / (double)n_live, 1.0);
           double v = 0.5 * t.urgency + 0.3 * scar - 0.4 * dc;
           v = fmin(fmax(v, -0.35), 0.35);
-          const bool edge = ((t.info & 255) < 32) & (g.rank < 16) & (capv > 0);
+          const bool edge = ((t.info & 255) < PAD_T) & (g.rank < PAD_A) & (capv > 0);
           score = edge ? (double)(float)v : 0.0;
         }
         if (mode == 2) {  // (uniform)

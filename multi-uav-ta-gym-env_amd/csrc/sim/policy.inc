@@ -13,7 +13,8 @@
   // One PAIR per lane: the lane keeps its pair's 128 hidden activations in registers and walks the chains by itself, the weights are
   // wave-uniform scalar operands streamed through the scalar cache.  So a logit is a pure function of its 25 (20) inputs and the
   // weights — the same instruction sequence whatever the lane, the batch, the position in the valid list or the env — and no value
-  // crosses lanes anywhere in the forward pass.  The valid pairs of the 16 x 32 grid are compacted first (row-major), 64 per pass.
+  // crosses lanes anywhere in the forward pass.  The valid pairs of the 16 x 32 grid (wide pads: 48 x 64) are compacted first (row-major), 64
+  // per pass: a pad row or column — the 24 x 48 tile has fewer agents and slots than the wide pads — has no valid pair and costs no pass.
   // ====================================================================================================
   typedef const __attribute__((address_space(4))) float pol_cf;  // constant address space: uniform indices become scalar loads
   typedef float pol_f2 __attribute__((ext_vector_type(2)));
@@ -187,18 +188,18 @@
   //   pair = cat([agent_feats[i], task_feats[j], a_pool, t_pool, context]);  logits = pair_mlp(pair)   Linear(58|41, 192) - ReLU - Linear(192, 192) - ReLU - Linear(192, 1)
   // plan(), the tokens, edge_valid, the scored Hungarian and the gate are PairCostHybrid's.  CONTRACT (DESIGN.md §7.1; tests/policy_mlp_py.py):
   //   * pool[d]: s = 0.0f; s = s + x[row][d] in float32 over the rows whose mask is 0, ascending row; pool[d] = s / (float)max(count, 1), IEEE division
-  //     (a_pool over the 16 agent rows, t_pool over the 32 task rows); context = what Sim::context(raw, 32, .) writes;
+  //     (a_pool over the 16 agent rows, t_pool over the 32 task rows; the wide variant: 48 and 64); context = what Sim::context(raw, 32 | 64, .) writes;
   //   * layer 1: one fmaf chain per output from the bias over a_pool, t_pool, context, the agent row, the task row (each ascending) — the
   //     env-uniform inputs first, the state_dict's columns (agent, task, a_pool, t_pool, context) are permuted when the weights are packed;
   //   * ReLU, layers 2 and 3, tanhf, the masked pairs: as above.
   // context_prefix: the 25 + 8 (raw: 20 + 1) env-uniform inputs into the env's scratch block behind the MLP-Pair layout (PolContextPair::PRE).  One
   // column per lane; the forward pass reads them back with vector loads (every lane the same address) and runs the chains' env-uniform
   // head once per plan (pair_forward_t).
-  template <bool RAW>
+  template <bool RAW, class POL>
   DEV void context_prefix_t(float* base) {
-    typedef PolContextPair::Blk B;
-    constexpr int Da = PolContextPair::da(RAW), Dt = PolContextPair::dt(RAW);
-    float* pre = base + PolContextPair::PRE;
+    typedef typename POL::Blk B;
+    constexpr int Da = POL::da(RAW), Dt = POL::dt(RAW);
+    float* pre = base + POL::PRE;
     if (lane < Da + Dt) {
       const bool ag = lane < Da;
       const int d = ag ? lane : lane - Da, rows = ag ? B::MA : B::MT, D = ag ? Da : Dt;
@@ -213,9 +214,10 @@
     context(RAW ? 1 : 0, B::MT, pre + Da + Dt);
     cold_sync();  // the columns are in memory before the forward pass reads them across lanes
   }
+  template <class POL>
   DEV void context_prefix(const PairPolicyDev& pol, float* base) {
-    if (pol.raw) context_prefix_t<true>(base);  // (uniform)
-    else context_prefix_t<false>(base);
+    if (pol.raw) context_prefix_t<true, POL>(base);  // (uniform)
+    else context_prefix_t<false, POL>(base);
   }
   // ---- MLP-Coalition: AttentionEscort(use_attention=False) (TaskAllocation/Hybrid/AttentionEscort.py:326-367,370-524) ---------------------------
   //   logits = pair_mlp(cat([agent_feats[i], task_feats[j]]))      Linear(38, 256) - ReLU - Linear(256, 256) - ReLU - Linear(256, 1)
@@ -230,7 +232,7 @@
     else if (pol.raw) pair_forward_t<true, POL>(pol, base, scores, logits, fill);  // (uniform)
     else pair_forward_t<false, POL>(pol, base, scores, logits, fill);
   }
-  // POL's tokens — build_pair_tokens(env, 32, 16[, raw]) or build_escort_tokens(env, 48, 16) — of the current state into this env's scratch block
+  // POL's tokens — build_pair_tokens(env, 32, 16[, raw]) (wide: 64, 48) or build_escort_tokens(env, 48, 16) — of the current state into this env's scratch block
   template <class POL>
   DEV void policy_tokens(const PairPolicyDev& pol, float* base) {
     typedef typename POL::Blk B;
@@ -257,7 +259,7 @@
     typedef typename POL::Blk B;
     if (gate_fires(POL::GATE, interval)) {
       policy_tokens<POL>(pol, scratch);
-      if constexpr (POL::np(false) > 0) context_prefix(pol, scratch);
+      if constexpr (POL::np(false) > 0) context_prefix<POL>(pol, scratch);
       policy_forward<POL>(pol, scratch, scratch + B::SCORES, nullptr, POL::FILL);
       cold_sync();  // the scores are in memory before the cost evaluation reads them across lanes
     }

@@ -23,11 +23,13 @@ from .batched import BatchedMultiUAVEnv, MuavtaError
 class InFlightRollouts:
     LANES = 2  # batches a handle keeps in flight
 
-    def __init__(self, config, n_envs: int, handles: int = 1, device: int = 0, allocator: str = "hungarian", **kw):
+    def __init__(self, config, n_envs: int, handles: int = 1, device: int = 0, allocator: str = "hungarian", token_pads=None, **kw):
         if handles < 1:
             raise ValueError("handles >= 1")
         self.envs = [BatchedMultiUAVEnv(config, n_envs, device=device, **kw) for _ in range(handles)]
         for e in self.envs:
+            if token_pads is not None:  # BatchedMultiUAVEnv.set_token_pads: (max_tasks, max_agents) of 'urgency_pair'; both lanes carry it
+                e.set_token_pads(*token_pads)
             e.set_allocator(allocator)
             e.set_lanes(2)
         self.n_envs = n_envs

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Register / spill / scratch / LDS figures of every kernel in a built libmuavta.so, read from the code object's metadata
 (builder's tool; no recompile).  usage: kernel_meta.py [path/to/libmuavta.so] [substring ...]
-       kernel_meta.py NEW.so --diff OLD.so    both tables row by row, then every function's instruction stream (see diff())"""
+       kernel_meta.py NEW.so --diff OLD.so    both tables row by row, then every function's instruction stream (see diff())
+       kernel_meta.py NEW.so --diff OLD.so --by-name   the same with the functions matched by name: for a build that ADDS instantiations"""
 import os
 import re
 import subprocess
@@ -13,8 +14,9 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 # The template arguments behind the tile — k_rollout<TL, REC, AL>, k_allocate<TL, AL>, k_pair_scores<TL, POL> — printed as the tags the
 # committed tables use: REC = the recording rollout, BL = AllocBaseline, PM = AllocLearned<POL>, and with it (or for k_pair_scores alone)
-# CX = PolContextPair, CO = PolCoalition.  AllocHungarian and PolPair print nothing.
-TAGS = (("REC", "Lb1E"), ("BL", "AllocBaseline"), ("PM", "AllocLearned"), ("CX", "PolContextPair"), ("CO", "PolCoalition"))
+# CX = PolContextPair, CO = PolCoalition, W = the variant over the wide 48 x 64 token pads (PolPairWide, PolContextPairWide), UW =
+# AllocUrgencyWide (Urgency-Pair at those pads).  AllocHungarian and PolPair print nothing.
+TAGS = (("REC", "Lb1E"), ("BL", "AllocBaseline"), ("UW", "AllocUrgencyWide"), ("PM", "AllocLearned"), ("CX", "PolContextPair"), ("CO", "PolCoalition"), ("W", "PairWide"))
 
 
 def short(name):
@@ -96,11 +98,56 @@ def diff(new, old):
     return 1 if bad else 0
 
 
+def diff_by_name(new, old):
+    """diff() for a build that adds kernels: every kernel of `old` must be in `new` under the same name with the same table row and the
+    same instruction stream (the k-th function of a name against the k-th of that name); what only `new` has is listed with its row.
+    Exit status 1 if a kernel of `old` is missing or differs in its row; differing streams are listed and counted, not fatal here: the
+    caller decides which kernels may change."""
+    ta, tb = table(new), table(old)
+    rows_b = {r.split()[0]: r for r in tb[1:]}
+    names_a = [r.split()[0] for r in ta[1:]]
+    print(f"new: {new}\nold: {old}\n\n(a) kernel table: {len(ta) - 1} kernels new, {len(tb) - 1} old")
+    print(ta[0])
+    bad = 0
+    for r in ta[1:]:
+        b = rows_b.get(r.split()[0])
+        print(r + ("   <-- NEW" if b is None else "" if b == r else f"   <-- old: {b}"))
+        bad |= b is not None and b != r
+    for n in rows_b:
+        if n not in names_a:
+            print(f"MISSING {n}")
+            bad = 1
+
+    def grouped(funcs):
+        g = {}
+        for sym, body in funcs:
+            g.setdefault(short(sym), []).append(body)
+        return g
+    ga, gb = grouped(streams(new)), grouped(streams(old))
+    same = differ = 0
+    print(f"\n(b) instruction streams by name: {sum(map(len, ga.values()))} functions new, {sum(map(len, gb.values()))} old")
+    for n, bodies in gb.items():
+        for k, ib in enumerate(bodies):
+            ia = ga.get(n, [])[k] if k < len(ga.get(n, [])) else None
+            if ia == ib:
+                same += 1
+                continue
+            differ += 1
+            if ia is None:
+                print(f"MISSING {n}")
+                bad = 1
+            else:
+                first = next((i for i, (x, y) in enumerate(zip(ia, ib)) if x != y), min(len(ia), len(ib)))
+                print(f"DIFFERENT {n}: {len(ia)} against {len(ib)} instructions, {sum(x != y for x, y in zip(ia, ib))} differ in place, first at {first}")
+    print(f"{same} of {same + differ} functions of the old build identical instruction for instruction in the new one" + ("" if differ else " (all)"))
+    return bad
+
+
 def main():
     args = sys.argv[1:]
     if "--diff" in args:
         i = args.index("--diff")
-        sys.exit(diff(args[0], args[i + 1]))
+        sys.exit((diff_by_name if "--by-name" in args else diff)(args[0], args[i + 1]))
     so = args[0] if args and args[0].endswith(".so") else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "multi-uav-ta-gym-env_amd", "libmuavta.so")
     print("\n".join(table(so, [a for a in args if not a.endswith(".so")])))
 
