@@ -246,8 +246,9 @@ int muavta_step_staged(MuavtaEnv* env); /* step with the actions muavta_allocate
  *   with kind = MUAVTA_TOK_PAIR(_RAW), max_agents 16, max_tasks 32, MUAVTA_SC_EDGE_VALID_ONLY, MUAVTA_GATE_TRAINER; n_replans counts the
  *   HungarianAllocator's plans, as in MUAVTA_ALLOC_URGENCY_PAIR.  Needs muavta_set_pair_policy first (else MUAVTA_E_STATE) — or
  *   muavta_set_context_pair_policy: the mode runs the installed learned policy, MLP-Pair, MLP-ContextPair or MLP-Coalition (below;
- *   the last one with the escort tokens, the escort gate and commit locks instead); kernel instantiations of its own; muavta_rollout_record returns MUAVTA_E_ARG.  Attention nets (AttPairNet), exploration noise and the
- *   value head are out of scope. */
+ *   the last one with the escort tokens, the escort gate and commit locks instead); kernel instantiations of its own; muavta_rollout_record returns MUAVTA_E_ARG for its token and
+ *   observation rings and records the RL transitions of an MLP-Pair / MLP-ContextPair instead (MuavtaRecord.rl: exploration noise enters there and only
+ *   there).  Attention nets (AttPairNet) and the value head are out of scope. */
 enum { MUAVTA_ALLOC_HUNGARIAN = 0, MUAVTA_ALLOC_URGENCY_PAIR = 1, MUAVTA_ALLOC_URGENCY_COALITION = 2, MUAVTA_ALLOC_HUNGARIAN_GATED = 3,
        MUAVTA_ALLOC_CAP_GREEDY = 4, MUAVTA_ALLOC_PI = 5, MUAVTA_ALLOC_MLP_PAIR = 6 };
 int muavta_set_allocator(MuavtaEnv* env, int32_t mode);
@@ -668,8 +669,41 @@ int muavta_device_ptrs(MuavtaEnv* env, void** state, void** obs_tasks, void** ob
  * (train_pair_cost.py:108,139), so the slots after the last step carry no sample — they are written as all-pad rows (masks 1,
  * ids -1, features / edge_valid / expert_mask 0, n_urgent 0, replanned 0) and s_wps carries the final value forward (the
  * step reward of those slots is exactly 0); no slot of any ring is left uninitialised.
- * Asynchronous on the handle's stream (muavta_sync / an event before reading). */
+ * Asynchronous on the handle's stream (muavta_sync / an event before reading).
+ *
+ * The RL half (rec->rl, MuavtaRlRings): run_rl_episode (experiments/train_pair_cost.py:131-156) under the installed learned policy, in
+ * MUAVTA_ALLOC_MLP_PAIR mode.  The launch is muavta_rollout's, and slot k of the caller's DEVICE rings [n_slots][N][...] receives the
+ * transition of env e's k-th replan gate (k = 0, 1, ...; a gate: _should_replan fired — the reference's `tok is not None`, `replanned` = 1
+ * of muavta_rl_run_device — whether or not the Hungarian then returned pairs), what PairCostHybrid.push stores (PairCostHybrid.py:391-408):
+ *   task_feats f32 [..][32][13|9], task_mask u8 [..][32], agent_feats f32 [..][16][12|11], agent_mask u8 [..][16], edge_valid f32 [..][16][32]
+ *                      build_tokens(env) at the gate, in muavta_tokens_device's layouts (kind MUAVTA_TOK_PAIR, or _PAIR_RAW for raw features)
+ *   context f32 [..][8|1]   what muavta_context_device gives there: required with an MLP-ContextPair policy, NULL with an MLP-Pair
+ *   logits, scores f32 [..][16][32]   the policy's outputs; 0 where edge_valid is 0 (those cells are not evaluated)
+ *   noise f32 [..][16][32]  INPUT AND OUTPUT, may be NULL: the caller's exploration draws (PairCostHybrid.act(explore=True), :266-278, e.g.
+ *                      randn * explore_std).  At a recorded gate an evaluated cell scores tanhf(logit + noise) * score_clamp — the sum is ONE
+ *                      float32 addition — and the launch writes 0 into the cells that were not evaluated, so that the slot then holds
+ *                      noise * edge_valid, the value the reference pushes.  NULL: the scores are muavta_pair_scores' bit for bit
+ *   selected f32 [..][16][32]   _selected_mask(tok, result)
+ *   s_wps_before, s_wps_after f64 [..]   compute_s_wps() before and after the env step that follows the gate (step reward = difference / 20)
+ *   next_task_feats .. next_edge_valid, next_context   build_tokens(env) (and the context) after that step, also when it ended the episode
+ *   done u8 [..]       bit 0 terminated, bit 1 truncated, after that step
+ *   step i32 [..]      the env's time_steps at the gate; pre-filled with -1 on the launch's stream: -1 marks a slot that was not written
+ *   n_gates i32 [N]    the gates that fired in this launch, COUNTED PAST n_slots
+ * Gates k >= n_slots are planned without noise and are not recorded (n_gates[e] > n_slots tells); nothing is written at or past slot
+ * n_slots, and the episode is the one a launch with more slots plays from there on.  Accepted only in MUAVTA_ALLOC_MLP_PAIR mode with an
+ * MLP-Pair or MLP-ContextPair installed, at the (32, 16) token pads, with kind < 0 and no observation ring, every ring but noise (and, by
+ * policy kind, context / next_context) non-NULL and 1 <= n_slots <= 4096; anything else is MUAVTA_E_ARG with the reason in
+ * muavta_last_error, and the handle stays usable.  Without rec->rl the call refuses the learned modes as before. */
 #define MUAVTA_OBS_UNWRITTEN 0x80
+#define MUAVTA_RL_MAX_SLOTS 4096
+typedef struct MuavtaRlRings {
+  int32_t n_slots, reserved;
+  float* task_feats; uint8_t* task_mask; float* agent_feats; uint8_t* agent_mask; float* edge_valid; float* context;
+  float* logits; float* scores; float* noise; float* selected;
+  double* s_wps_before; double* s_wps_after;
+  float* next_task_feats; uint8_t* next_task_mask; float* next_agent_feats; uint8_t* next_agent_mask; float* next_edge_valid; float* next_context;
+  uint8_t* done; int32_t* step; int32_t* n_gates;
+} MuavtaRlRings;
 typedef struct MuavtaRecord {
   int32_t kind, max_tasks, max_agents, reserved;  /* MUAVTA_TOK_* or -1, token pads */
   float* task_feats; uint8_t* task_mask; int32_t* task_ids;
@@ -677,6 +711,7 @@ typedef struct MuavtaRecord {
   float* edge_valid; int32_t* n_urgent; float* expert_mask; int32_t* replanned;
   double* s_wps;
   float* obs_tasks; uint64_t* obs_legal; uint8_t* obs_pad; float* obs_agents; float* obs_flags; double* obs_reward; uint8_t* obs_done;
+  const MuavtaRlRings* rl;  /* NULL, or the RL transition rings of the learned pair policies (above); appended: a zero-initialised record behaves as before */
 } MuavtaRecord;
 int muavta_rollout_record(MuavtaEnv* env, const uint64_t* seeds, int32_t n_steps, int32_t replan_interval, int32_t use_visibility,
                           int32_t write_obs, const MuavtaRecord* rec);

@@ -160,7 +160,7 @@ class BatchedMultiUAVEnv:
         max_tasks_per_agent=1 under its own should_replan gate, replan_interval = its interval; wps_eval.py:147-159).  In the
         two baseline modes rollout_record raises MuavtaError.
         'mlp_pair' runs whatever learned policy `set_pair_policy` installed (a kind of `POLICY_KINDS`: its forward pass inside the kernel,
-        under that kind's gate with replan_interval) and needs one installed first; rollout_record raises MuavtaError in it too.
+        under that kind's gate with replan_interval) and needs one installed first; rollout_record raises MuavtaError in it too (`rollout_rl_record` records this mode's RL transitions).
         'mlp_context_pair' and 'mlp_coalition' are the same mode and raise unless the installed policy is of their kind — a check on this
         object's record of its last `set_pair_policy`, not on the handle: a policy installed or cleared through the C entry points
         directly is not seen by it."""
@@ -718,6 +718,85 @@ class BatchedMultiUAVEnv:
             if s.shape != (self.n_envs,):
                 raise ValueError(f"seeds must have shape ({self.n_envs},)")
         self._ck(self.L.muavta_rollout_record(self.h, _vp(s), int(n_steps), int(replan_interval), int(use_visibility), int(write_obs), C.byref(rec)))
+
+    RL_MAX_SLOTS = 4096  # include/muavta.h: MuavtaRlRings.n_slots
+
+    def _rl_record_policy(self, who: str):
+        """the installed policy, if `rollout_rl_record` can run it (ValueError otherwise: none of these needs a device call)"""
+        kind = self._policy_kind()
+        if kind is None:
+            raise ValueError(f"{who}: no policy is installed (set_pair_policy first)")
+        if kind.name == "coalition":
+            raise ValueError(f"{who}: the RL transitions are recorded for MLP-Pair and MLP-ContextPair; the installed policy is an MLP-Coalition")
+        if self.token_pads != self.TOKEN_PADS[0]:
+            raise ValueError(f"{who}: the RL transitions are recorded at the (32, 16) token pads; the handle is set to {self.token_pads}")
+        return kind
+
+    def rl_record_shapes(self, n_slots: int):
+        """name -> (shape, numpy dtype) of the rings `rollout_rl_record` fills for the installed policy: G = n_slots gates per env,
+        `context` / `next_context` only for an MLP-ContextPair."""
+        kind = self._rl_record_policy("rl_record_shapes")
+        G, N = int(n_slots), self.n_envs
+        if not 1 <= G <= self.RL_MAX_SLOTS:
+            raise ValueError(f"rl_record_shapes: n_slots = {G}; 1 .. {self.RL_MAX_SLOTS}")
+        mt, ma = self.TOKEN_PADS[0]
+        raw = bool(self._pair_policy["raw_features"])
+        _, dt, da = self.TOKEN_KINDS["pair_raw" if raw else "pair"]
+        tok = {"task_feats": ((G, N, mt, dt), np.float32), "task_mask": ((G, N, mt), np.uint8), "agent_feats": ((G, N, ma, da), np.float32),
+               "agent_mask": ((G, N, ma), np.uint8), "edge_valid": ((G, N, ma, mt), np.float32)}
+        if kind.name == "context":
+            tok["context"] = ((G, N, 1 if raw else 8), np.float32)
+        grid = ((G, N, ma, mt), np.float32)
+        shapes = dict(tok)
+        shapes.update({"logits": grid, "scores": grid, "selected": grid, "s_wps_before": ((G, N), np.float64), "s_wps_after": ((G, N), np.float64)})
+        shapes.update({"next_" + n: v for n, v in tok.items()})
+        shapes.update({"done": ((G, N), np.uint8), "step": ((G, N), np.int32), "n_gates": ((N,), np.int32)})
+        return shapes
+
+    def rollout_rl_record(self, seeds: Optional[Sequence[int]], n_steps: int, replan_interval: int, use_visibility: bool, rings: dict, noise=None, write_obs: bool = False):
+        """muavta_rollout_record with MuavtaRlRings: the fused rollout under the installed MLP-Pair / MLP-ContextPair policy ('mlp_pair' mode)
+        that also leaves, for every env, the transition of its k-th replan gate in slot k of `rings` — what run_rl_episode pushes
+        (experiments/train_pair_cost.py:131-156): tokens (+ context), logits, scores, selected, S_WPS before / after the step, next tokens,
+        done — plus `step` (the gate's time step; -1: slot not written) and `n_gates` [N] (gates that fired, counted past the slots).
+        `rings`: contiguous CUDA torch tensors with the shapes of `rl_record_shapes(G)`; G is read from `rings['step']`.  `noise`: f32
+        [G, N, 16, 32] of exploration draws, or None: score = tanhf(logit + noise) * score_clamp at the recorded gates, and the launch writes 0 into it
+        where the cell was not evaluated (noise * edge_valid, what the reference pushes).  Gates past slot G - 1 are planned without noise
+        and not recorded.  `write_obs` as in `rollout`.  Asynchronous on the handle's stream: `sync()` before reading the rings from another stream."""
+        from .params import MuavtaRecord, MuavtaRlRings
+
+        who = "rollout_rl_record"
+        self._rl_record_policy(who)
+        if self._alloc_mode != self.ALLOCATORS["mlp_pair"]:
+            raise ValueError(f"{who}: the allocator must be 'mlp_pair' (set_allocator)")
+        if "step" not in rings or rings["step"].dim() != 2:
+            raise ValueError(f"{who}: rings['step'] must be an int32 tensor of shape (n_slots, {self.n_envs})")
+        G = int(rings["step"].shape[0])
+        want = self.rl_record_shapes(G)
+        if noise is not None:
+            want["noise"] = want["scores"]
+        rl = MuavtaRlRings()
+        rl.n_slots = G
+        for name, (shape, dtype) in want.items():
+            t = noise if name == "noise" else rings.get(name)
+            if t is None:
+                raise ValueError(f"{who}: rings lacks '{name}'")
+            if tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous() or t.element_size() != np.dtype(dtype).itemsize \
+                    or t.dtype.is_floating_point != (np.dtype(dtype).kind == "f"):
+                raise ValueError(f"{who}: {name} must be a contiguous CUDA tensor of shape {shape}, {np.dtype(dtype).name}")
+            if t.device.index != self.device_index:
+                raise ValueError(f"{who}: {name} lives on {t.device}, the env batch on cuda:{self.device_index}")
+            setattr(rl, name, t.data_ptr())
+        s = None
+        if seeds is not None:
+            s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
+            if s.shape != (self.n_envs,):
+                raise ValueError(f"seeds must have shape ({self.n_envs},)")
+        rec = MuavtaRecord()
+        rec.kind = -1
+        rec.rl = C.pointer(rl)
+        self.escalated = {}
+        self._esc_rows = None
+        self._ck(self.L.muavta_rollout_record(self.h, _vp(s), int(n_steps), int(replan_interval), int(use_visibility), int(bool(write_obs)), C.byref(rec)))
 
     # ------------------------------------------------------------------ sub-batches on their own streams
     def set_parts(self, n_parts: int):

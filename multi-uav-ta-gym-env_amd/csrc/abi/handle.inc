@@ -73,7 +73,7 @@ struct MuavtaEnv {
   DevBuf<uint32_t> d_pace;
   uint32_t pace_epoch = 0;
   enum { REC_SLOT = 256 };
-  DevBuf<void> d_rec;  // [2][REC_SLOT]: slot 0 all zero (plain rollouts), slot 1 the RecordPtrs of the muavta_rollout_record launch in flight
+  DevBuf<void> d_rec;  // [3][REC_SLOT]: slot 0 all zero (plain rollouts), slot 1 the RecordPtrs of the muavta_rollout_record launch in flight, slot 2 the RlRingsDev of one with RL rings
   DevBuf<uint64_t> d_seeds[2];
   DevBuf<int32_t> d_act_agent, d_act_index, d_call_out;
   DevBuf<int32_t> d_list_agent, d_list_index;  // muavta_step_lists rows [N][list_cap] (grown on demand)
@@ -202,6 +202,7 @@ int launch_attr(MuavtaEnv* e) {
     for_each_wide_policy(policy);
     allocator(AllocUrgencyWide{}); allow(&k_rollout<TL, true, AllocUrgencyWide>, 0);
   }
+  allow(&k_rollout<TL, false, AllocLearnedRl<PolPair>>, 0); allow(&k_rollout<TL, false, AllocLearnedRl<PolContextPair>>, 0);  // (the RL rings of muavta_rollout_record)
   if (lds > 48 * 1024)
     for (const auto& k : ks) HIPCHK(e, hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + k.second)));
   return MUAVTA_OK;
@@ -535,8 +536,8 @@ static int create_lane(const MuavtaParams* params, int32_t n_envs, int32_t devic
     CK(e->d_pace.alloc((size_t)PACE_KEYS * 16 * sizeof(uint32_t)));
     CK(hipMemsetAsync(e->d_pace, 0, (size_t)PACE_KEYS * 16 * sizeof(uint32_t), e->stream));  // epoch 0 is never issued
     h.P = e->P; h.O = e->O; h.tapes = e->tapes; h.blobs = e->blobs; h.cold = e->cold; h.pace = e->d_pace;
-    CK(e->d_rec.alloc(2 * MuavtaEnv::REC_SLOT));
-    CK(hipMemsetAsync(e->d_rec, 0, 2 * MuavtaEnv::REC_SLOT, e->stream));
+    CK(e->d_rec.alloc(3 * MuavtaEnv::REC_SLOT));
+    CK(hipMemsetAsync(e->d_rec, 0, 3 * MuavtaEnv::REC_SLOT, e->stream));
     CK(e->d_ctx.alloc(sizeof(DevCtx)));
     CK(hipMemcpyAsync(e->d_ctx, &h, sizeof(DevCtx), hipMemcpyHostToDevice, e->stream));
     CK(hipStreamSynchronize(e->stream));  // `h` is a stack object

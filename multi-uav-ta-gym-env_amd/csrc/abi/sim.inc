@@ -66,6 +66,25 @@ static void launch_rollout(MuavtaEnv* e, const Target& t, const uint64_t* ds, in
                            const MuavtaRecord* rec) {
   const int epoch = (int)(e->pace_epoch++ % 65535u) + 1;  // 1..65535: the zero-filled table matches no launch
   char* slot = (char*)e->d_rec.p;  // slot 0, all zero: nothing to record
+  if (rec && rec->rl) {  // the RL rings (rollout_record_rl has checked them): slot 2, and the recording instantiation of the installed policy's kind
+    const MuavtaRlRings& r = *rec->rl;
+    RlRingsDev R;
+    memset(&R, 0, sizeof(R));
+    R.tok = {r.task_feats, r.task_mask, r.agent_feats, r.agent_mask, r.edge_valid, r.context};
+    R.next = {r.next_task_feats, r.next_task_mask, r.next_agent_feats, r.next_agent_mask, r.next_edge_valid, r.next_context};
+    R.logits = r.logits; R.scores = r.scores; R.noise = r.noise; R.selected = r.selected;
+    R.s_wps_before = r.s_wps_before; R.s_wps_after = r.s_wps_after; R.done = r.done; R.step = r.step; R.n_gates = r.n_gates;
+    R.n_slots = r.n_slots; R.n_envs = e->n_envs;
+    RecBlob blob;
+    memset(&blob, 0, sizeof(blob));
+    memcpy(&blob, &R, sizeof(R));
+    slot += 2 * MuavtaEnv::REC_SLOT;
+    hipLaunchKernelGGL(k_store_rec, dim3(1), dim3(64), 0, t.stream, blob, (uint32_t*)slot);  // (by value, stream-ordered: see below)
+    const RolloutFn<TL> rl_fn = e->pol_kind == POL_CONTEXT_PAIR ? &k_rollout<TL, false, AllocLearnedRl<PolContextPair>> : &k_rollout<TL, false, AllocLearnedRl<PolPair>>;
+    hipLaunchKernelGGL(rl_fn, dim3(t.count), dim3(WG), extra_lds, t.stream, (const DevCtx*)e->d_ctx, ds, n_steps, interval, use_vis, e->alloc_mode, write_obs,
+                       (double*)e->d_metrics, sb, (const RecordPtrs<TL>*)slot, epoch, t.first);
+    return;
+  }
   if (rec) {
     RecordPtrs<TL> R;
     memset(&R, 0, sizeof(R));
@@ -381,6 +400,10 @@ static int rollout_impl(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, in
   // muavta_rollout_record's obs_done pre-fill: on the stream of the lane that runs the kernel, so only after the lane decision above
   if (rec && rec->obs_done && n_steps > 0)
     HIPCHK(e, hipMemsetAsync(rec->obs_done, MUAVTA_OBS_UNWRITTEN, (size_t)n_steps * (size_t)e->n_envs, e->stream));
+  if (rec && rec->rl) {  // the RL rings' pre-fill, likewise: step = -1 in every slot (not written), no gate counted yet
+    HIPCHK(e, hipMemsetAsync(rec->rl->step, 0xFF, (size_t)rec->rl->n_slots * (size_t)e->n_envs * sizeof(int32_t), e->stream));
+    HIPCHK(e, hipMemsetAsync(rec->rl->n_gates, 0, (size_t)e->n_envs * sizeof(int32_t), e->stream));
+  }
   const int evi = (int)(e->n_rollouts % MuavtaEnv::EV_RING);
   HIPCHK(e, hipEventRecord(e->ev0[evi], e->stream));
   static const size_t extra_lds = getenv("MUAVTA_EXTRA_LDS") ? (size_t)atoi(getenv("MUAVTA_EXTRA_LDS")) : 0;  // occupancy experiments only
@@ -400,8 +423,27 @@ static int rollout_impl(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, in
 int muavta_rollout(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, int32_t interval, int32_t use_vis, int32_t write_obs) {
   return rollout_impl(e, seeds, n_steps, interval, use_vis, write_obs, nullptr);
 }
+// muavta_rollout_record with rec->rl: everything that is not the one accepted combination is refused here, with its reason
+static int rollout_record_rl(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, int32_t interval, int32_t use_vis, int32_t write_obs, const MuavtaRecord* rec) {
+  const MuavtaRlRings& r = *rec->rl;
+  const char* why = nullptr;
+  if (rec->kind >= 0 || rec->obs_tasks || rec->obs_legal || rec->obs_pad || rec->obs_agents || rec->obs_flags || rec->obs_reward || rec->obs_done)
+    why = "the RL rings come alone (kind < 0, no observation rings)";
+  else if (e->alloc_mode != MUAVTA_ALLOC_MLP_PAIR) why = "the RL rings need the MUAVTA_ALLOC_MLP_PAIR allocator (muavta_set_allocator)";
+  else if (e->pol_kind != POL_PAIR && e->pol_kind != POL_CONTEXT_PAIR) why = "the RL rings are recorded for an MLP-Pair or MLP-ContextPair policy, not for an MLP-Coalition";
+  else if (wide_pads(e)) why = "the RL rings are recorded at the (32, 16) token pads only (muavta_set TOKEN_PADS)";
+  else if (r.n_slots < 1 || r.n_slots > MUAVTA_RL_MAX_SLOTS) why = "the RL rings need 1 <= n_slots <= 4096";
+  else if (!(r.task_feats && r.task_mask && r.agent_feats && r.agent_mask && r.edge_valid && r.logits && r.scores && r.selected && r.s_wps_before && r.s_wps_after &&
+             r.next_task_feats && r.next_task_mask && r.next_agent_feats && r.next_agent_mask && r.next_edge_valid && r.done && r.step && r.n_gates))
+    why = "an RL ring is NULL (only noise may be; context / next_context follow the policy's kind)";
+  else if (e->pol_kind == POL_CONTEXT_PAIR && !(r.context && r.next_context)) why = "an MLP-ContextPair policy needs the context and next_context rings";
+  else if (e->pol_kind == POL_PAIR && (r.context || r.next_context)) why = "an MLP-Pair policy has no context: context and next_context must be NULL";
+  if (why) { e->err = std::string("muavta_rollout_record: ") + why; return MUAVTA_E_ARG; }
+  return rollout_impl(e, seeds, n_steps, interval, use_vis, write_obs, rec);  // (pre-fills step and n_gates once the lane is chosen)
+}
 int muavta_rollout_record(MuavtaEnv* e, const uint64_t* seeds, int32_t n_steps, int32_t interval, int32_t use_vis, int32_t write_obs, const MuavtaRecord* rec) {
   int dt, da;
+  if (e && rec && rec->rl) return rollout_record_rl(e, seeds, n_steps, interval, use_vis, write_obs, rec);
   bool bad = !e || !rec;
   if (!bad && rec->kind >= 0)
     bad = token_dims(rec->kind, &dt, &da) || rec->max_tasks < 1 || rec->max_agents < 1 || rec->max_tasks > 4096 || rec->max_agents > 4096 ||

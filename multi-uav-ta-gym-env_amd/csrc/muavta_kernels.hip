@@ -302,6 +302,12 @@ struct AllocUrgencyWide { enum { EXTRA_LDS = 0, MAX_WAVES = 8, WIDE = 1 }; };
 struct AllocBaseline { enum { EXTRA_LDS = 0, MAX_WAVES = 8, WIDE = 0 }; };   // MUAVTA_ALLOC_CAP_GREEDY, _PI (sim/baselines.inc): the Hungarian kernels do not carry this code
 template <class POL>
 struct AllocLearned { typedef POL Pol; enum { EXTRA_LDS = SCORED_EXTRA_LDS, MAX_WAVES = POL::MAX_WAVES, WIDE = POL::WIDE }; };  // MUAVTA_ALLOC_MLP_PAIR (sim/policy.inc)
+// ... with the transition of every replan gate recorded (MuavtaRlRings of muavta_rollout_record): k_rollout only, PolPair and PolContextPair only.
+// A tag of its own, not a value of k_rollout's REC: every instantiation the library had before keeps its name.
+template <class POL>
+struct AllocLearnedRl : AllocLearned<POL> {};
+template <class AL> struct records_rl : std::false_type {};
+template <class POL> struct records_rl<AllocLearnedRl<POL>> : std::true_type {};
 // The one place that turns a tag into the allocator's call.  sc_list: EXTRA_LDS bytes of LDS behind the tile.  A macro on purpose: as a
 // function (free or a member of Sim, both tried) the helper is one more level for the inliner, and with it the instruction streams of 24 of
 // the code object's 83 functions change (every k_rollout but the baselines', every learned k_allocate; two swapped instructions in the
@@ -549,6 +555,72 @@ struct RecordPtrs {
 struct RecBlob { uint32_t w[64]; };  // 256 B: a RecordPtrs<TL> by value
 __global__ void k_store_rec(RecBlob b, uint32_t* dst) { dst[threadIdx.x] = b.w[threadIdx.x]; }
 
+// The RL half of muavta_rollout_record (MuavtaRlRings): per-GATE rings [n_slots][N][...] of the transitions run_rl_episode pushes
+// (experiments/train_pair_cost.py:131-156).  The pointers sit in a device slot of their own (the handle's third record slot) that the
+// instantiations with an AllocLearnedRl tag — and only they — are handed in place of a RecordPtrs.
+struct RlTokRings { float* task_feats; uint8_t* task_mask; float* agent_feats; uint8_t* agent_mask; float* edge_valid; float* context; };
+struct RlRingsDev {
+  RlTokRings tok, next;  // build_tokens(env) (+ the context vector) at the gate / after the step that follows it
+  float *logits, *scores, *noise, *selected;  // [n_slots][N][MA][MT]; noise: input and output, or null
+  double *s_wps_before, *s_wps_after;         // [n_slots][N]
+  uint8_t* done;                              // [n_slots][N]
+  int32_t *step, *n_gates;                    // [n_slots][N] (pre-filled with -1), [N] (pre-filled with 0)
+  int32_t n_slots, n_envs;
+};
+static_assert(sizeof(RlRingsDev) <= sizeof(RecBlob), "k_store_rec moves one RecBlob");
+// The token block of the plan in the env's scratch (policy_tokens; with env-uniform inputs: context_prefix behind it), complete and visible,
+// into row `at` = slot * N + env of a ring set.  The rows are compact in the block too: [MT][dt(raw)], [MA][da(raw)].
+template <class POL>
+__device__ __forceinline__ void rl_store_tokens(const RlTokRings& R, const PairPolicyDev& pol, const float* blk, size_t at) {
+  typedef typename POL::Blk B;
+  static_assert(B::MT <= WG && B::MA <= WG, "one pad-mask byte per lane");
+  const int lane = threadIdx.x, Dt = POL::dt(pol.raw != 0), Da = POL::da(pol.raw != 0);
+  float *tf = as_global(R.task_feats) + at * (size_t)(B::MT * Dt), *af = as_global(R.agent_feats) + at * (size_t)(B::MA * Da);
+  float* ev = as_global(R.edge_valid) + at * (size_t)(B::MA * B::MT);
+  for (int i = lane; i < B::MT * Dt; i += WG) tf[i] = blk[B::TF + i];
+  for (int i = lane; i < B::MA * Da; i += WG) af[i] = blk[B::AF + i];
+  for (int i = lane; i < B::MA * B::MT; i += WG) ev[i] = blk[B::EV + i];
+  const uint8_t *tm = reinterpret_cast<const uint8_t*>(blk + B::TMASK), *am = reinterpret_cast<const uint8_t*>(blk + B::AMASK);
+  if (lane < B::MT) as_global(R.task_mask)[at * B::MT + lane] = tm[lane];
+  if (lane < B::MA) as_global(R.agent_mask)[at * B::MA + lane] = am[lane];
+  if constexpr (POL::np(false) > 0) {  // the context vector: the tail of the env-uniform head of layer 1's input row
+    const int nc = pol.raw ? 1 : 8;
+    if (lane < nc) as_global(R.context)[at * nc + lane] = blk[POL::PRE + Da + Dt + lane];
+  }
+}
+// A gate fired and its tokens are in the scratch block: count it, and if it still has a slot, store what is known before the forward pass
+// (tokens, time step, S_WPS) and hand the slot's [MA][MT] blocks to the plan.  The count lives in n_gates[env] between the phases — no
+// register is carried across the step body — and is this wave's alone.
+template <class TL, class POL>
+__device__ __forceinline__ typename Sim<TL>::RlGate rl_gate_open(Sim<TL>& sim, const RlRingsDev& R, const PairPolicyDev& pol, const float* blk, int env) {
+  typename Sim<TL>::RlGate g{nullptr, nullptr, nullptr, nullptr};
+  int32_t* ng = as_global(R.n_gates) + env;
+  const int k = __builtin_amdgcn_readfirstlane(*ng);
+  if (threadIdx.x == 0) *ng = k + 1;
+  if (k >= R.n_slots) return g;  // (uniform)
+  const size_t at = (size_t)k * R.n_envs + env, cell0 = at * (size_t)(POL::Blk::MA * POL::Blk::MT);
+  rl_store_tokens<POL>(R.tok, pol, blk, at);
+  if (threadIdx.x == 0) { as_global(R.step)[at] = sim.tnow; as_global(R.s_wps_before)[at] = sim.s_wps(); }
+  g.scores = as_global(R.scores) + cell0; g.logits = as_global(R.logits) + cell0; g.selected = as_global(R.selected) + cell0;
+  if (R.noise) g.noise = as_global(R.noise) + cell0;
+  return g;
+}
+// The step that followed a gate is done: S_WPS and the done bits after it, and the tokens of the state it left (also of a final state, as the
+// reference builds them, :150-151).  The scratch block is free for that: the next gate rebuilds it, and no plan reads it in between.
+template <class TL, class POL>
+__device__ __forceinline__ void rl_after_step(Sim<TL>& sim, const RlRingsDev& R, const PairPolicyDev& pol, float* blk, int env) {
+  const int k = __builtin_amdgcn_readfirstlane(as_global(R.n_gates)[env]) - 1;  // the gate of the step just taken
+  if (k < 0 || k >= R.n_slots) return;  // (uniform)
+  const size_t at = (size_t)k * R.n_envs + env;
+  if (threadIdx.x == 0) {
+    as_global(R.s_wps_after)[at] = sim.s_wps();
+    as_global(R.done)[at] = (uint8_t)((sim.S.terminated ? 1 : 0) | (sim.S.truncated ? 2 : 0));
+  }
+  sim.template policy_tokens<POL>(pol, blk);
+  if constexpr (POL::np(false) > 0) sim.template context_prefix<POL>(pol, blk);
+  rl_store_tokens<POL>(R.next, pol, blk, at);
+}
+
 template <class TL, bool REC, class AL>
 __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned char* lds_own, uint32_t lds_base, int env, int phases, int interval, int use_vis, int mode,
                                                 const RecordPtrs<TL>& rec, int slot, int oslot) {
@@ -575,7 +647,17 @@ __device__ MUAVTA_PHASE_ATTR void rollout_phase(const DevCtx* ctxp, unsigned cha
     obs_for_env(sim, ctx.P, O, at, handle_buffer);
   }
   lds_sync();
+  if constexpr (records_rl<AL>::value) {  // (such a launch's `rec` is the handle's RlRingsDev slot)
+    if ((phases & PH_STEP) && L.S->gate_step == sim.tnow)  // (uniform) the gate fired at the step just taken: its transition is completed
+      rl_after_step<TL, typename AL::Pol>(sim, reinterpret_cast<const RlRingsDev&>(rec), ctx.pol, as_global(ctx.pol.scratch) + (size_t)env * AL::Pol::FLOATS, env);
+  }
   if (!ABL(9) && (phases & PH_ALLOC) && !(L.S->terminated || L.S->truncated)) {
+    if constexpr (records_rl<AL>::value) {
+      typedef typename AL::Pol POL;
+      float* blk = as_global(ctx.pol.scratch) + (size_t)env * POL::FLOATS;
+      sim.template allocate_learned_rl<POL>(interval, use_vis, ctx.pol, blk, reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS,
+                                            [&]() { return rl_gate_open<TL, POL>(sim, reinterpret_cast<const RlRingsDev&>(rec), ctx.pol, blk, env); });
+    } else
     RUN_ALLOCATOR(AL, sim, ctx, env, interval, use_vis, mode, reinterpret_cast<unsigned char*>(L.S) + Lds<TL>::bytes() + PROF_EXTRA_LDS);
     if (REC && rec.K.task_feats) {  // the sample of step `slot`: tokens + labels of the plan just staged, S_WPS before the step
       const typename Sim<TL>::TokPtrs K = global_tok_ptrs<TL>(rec.K);

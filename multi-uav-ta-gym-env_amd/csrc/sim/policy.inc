@@ -9,7 +9,8 @@
   //         acc = b[n];  for k = 0 .. K-1:  acc = fmaf(W[n][k], x[k], acc)
   //     layer 1's x is the reference's cat: the agent row's 12 (raw: 11) features, then the task row's 13 (raw: 9) — one chain, not an
   //     agent part plus a task part; ReLU is `acc > 0 ? acc : 0`; layer 3 runs n-ascending over layer 2's outputs;
-  //   * score = tanhf(logit) * score_clamp, float32, on the pairs whose edge_valid is 1; masked pairs are not evaluated at all.
+  //   * score = tanhf(logit) * score_clamp, float32, on the pairs whose edge_valid is 1; masked pairs are not evaluated at all;
+  //   * with exploration noise (the RL rings of muavta_rollout_record): score = tanhf(logit + noise) * score_clamp, the sum ONE float32 addition.
   // One PAIR per lane: the lane keeps its pair's 128 hidden activations in registers and walks the chains by itself, the weights are
   // wave-uniform scalar operands streamed through the scalar cache.  So a logit is a pure function of its 25 (20) inputs and the
   // weights — the same instruction sequence whatever the lane, the batch, the position in the valid list or the env — and no value
@@ -27,8 +28,10 @@
   // layer 1's input row (PolContextPair: `pre`, written by context_prefix() below, with the 192 floats of HEAD behind it), the score function and
   // the place of the list of valid cells (PolCoalition: 1,536 B do not fit in front of Scratch::resid) — everything else is the same code.
   // tpad / apad (POL::SIGMOID): the token builder's task_mask / agent_mask (1 = pad row); a pair of a pad row is masked like one whose edge_valid is 0.
+  // noise: this env's [16, MT] exploration draws of a recorded gate, or null: added to the logit of an evaluated cell under the tanhf (the logit
+  // that is written stays the network's) and set to 0 in every other cell — the slot then holds noise * edge_valid (PairCostHybrid.py:266-278).
   template <bool RAW, class POL>
-  DEV void pair_forward_t(const PairPolicyDev& pol, float* blk, float* scores, float* logits, bool fill) {
+  DEV void pair_forward_t(const PairPolicyDev& pol, float* blk, float* scores, float* logits, bool fill, float* noise = nullptr) {
     typedef typename POL::W LY;
     typedef typename POL::Blk B;
     constexpr int Da = POL::da(RAW), Dt = POL::dt(RAW), NP = POL::np(RAW), K0 = NP + Da + Dt, HID = LY::HID;
@@ -56,6 +59,7 @@
         if (scores) scores[c] = 0.f;
         if (logits) logits[c] = 0.f;
       }
+      if (noise && !v) noise[c] = 0.f;
       nv += __popcll(m);
     }
     // NP > 0: the first NP inputs of layer 1 (a_pool, t_pool, context) are the same for every pair of the env, so the chains' values after them
@@ -179,7 +183,7 @@
         if (logits) logits[c] = logit;
         if constexpr (POL::SIGMOID) {  // AttentionEscort.act: 1 / (1 + exp(-clip(logit, -20, 20))), float32, IEEE division
           if (scores) scores[c] = 1.0f / (1.0f + expf(-fminf(fmaxf(logit, -20.0f), 20.0f)));
-        } else if (scores) scores[c] = tanhf(logit) * clamp;
+        } else if (scores) scores[c] = tanhf(noise ? logit + noise[c] : logit) * clamp;
       }
     }
     lds_sync();
@@ -227,10 +231,10 @@
   //   pad pairs and pairs whose edge_valid is 0 are not evaluated and score 0; score_clamp is not used.
   // The forward pass of the installed policy over the env's scratch block (a network with env-uniform inputs: after context_prefix())
   template <class POL>
-  DEV void policy_forward(const PairPolicyDev& pol, float* base, float* scores, float* logits, bool fill) {
-    if constexpr (!POL::RAW_TOKENS) pair_forward_t<false, POL>(pol, base, scores, logits, fill);
-    else if (pol.raw) pair_forward_t<true, POL>(pol, base, scores, logits, fill);  // (uniform)
-    else pair_forward_t<false, POL>(pol, base, scores, logits, fill);
+  DEV void policy_forward(const PairPolicyDev& pol, float* base, float* scores, float* logits, bool fill, float* noise = nullptr) {
+    if constexpr (!POL::RAW_TOKENS) pair_forward_t<false, POL>(pol, base, scores, logits, fill, noise);
+    else if (pol.raw) pair_forward_t<true, POL>(pol, base, scores, logits, fill, noise);  // (uniform)
+    else pair_forward_t<false, POL>(pol, base, scores, logits, fill, noise);
   }
   // POL's tokens — build_pair_tokens(env, 32, 16[, raw]) (wide: 64, 48) or build_escort_tokens(env, 48, 16) — of the current state into this env's scratch block
   template <class POL>
@@ -265,6 +269,27 @@
     }
     ScoredDev sc;
     sc.scores = scratch + B::SCORES; sc.pri = nullptr; sc.reserved = nullptr; sc.selected = nullptr; sc.replanned = nullptr;
+    sc.kind = POL::tok_kind(pol.raw); sc.MT = B::MT; sc.MA = B::MA; sc.gate = POL::GATE; sc.flags = POL::FLAGS;
+    allocate<true>(interval, use_visibility, 4, &sc, 0, sc_list);
+  }
+  // The same plan with the gate's transition recorded (the RL rings of muavta_rollout_record; muavta_kernels.hip: rl_gate_open).  at_gate():
+  // called where the gate fired, between the token builder and the forward pass — it counts the gate and hands back this env's [16, MT]
+  // blocks of the slot it belongs to, or nothing past the last slot: such a gate is planned from the scratch block, without noise, as above.
+  // A recorded gate's scores are written to the slot itself, masked cells as 0, and the plan reads them there.
+  struct RlGate { float *scores, *logits, *noise, *selected; };
+  template <class POL, class F>
+  DEV void allocate_learned_rl(int interval, int use_visibility, const PairPolicyDev& pol, float* scratch, uint8_t* sc_list, F at_gate) {
+    typedef typename POL::Blk B;
+    RlGate g{nullptr, nullptr, nullptr, nullptr};
+    if (gate_fires(POL::GATE, interval)) {
+      policy_tokens<POL>(pol, scratch);
+      if constexpr (POL::np(false) > 0) context_prefix<POL>(pol, scratch);
+      g = at_gate();
+      policy_forward<POL>(pol, scratch, g.scores ? g.scores : scratch + B::SCORES, g.logits, g.scores ? true : (bool)POL::FILL, g.noise);  // (ONE call site)
+      cold_sync();  // the scores are in memory before the cost evaluation reads them across lanes
+    }
+    ScoredDev sc;
+    sc.scores = g.scores ? g.scores : scratch + B::SCORES; sc.pri = nullptr; sc.reserved = nullptr; sc.selected = g.selected; sc.replanned = nullptr;
     sc.kind = POL::tok_kind(pol.raw); sc.MT = B::MT; sc.MA = B::MA; sc.gate = POL::GATE; sc.flags = POL::FLAGS;
     allocate<true>(interval, use_visibility, 4, &sc, 0, sc_list);
   }

@@ -75,6 +75,43 @@ def il_record(env: BatchedMultiUAVEnv, seeds, n_steps: int = 150, interval: int 
     return out
 
 
+def rl_record(env: BatchedMultiUAVEnv, seeds, n_steps: int = 150, interval: int = 20, n_slots: Optional[int] = None, noise_std: Optional[float] = None,
+              generator=None, rings: Optional[dict] = None, device=None) -> dict:
+    """run_rl_episode (experiments/train_pair_cost.py:131-156) for the WHOLE episode batch in ONE launch, under the installed MLP-Pair /
+    MLP-ContextPair policy with `set_allocator('mlp_pair')` selected (`rollout_rl_record`): the forward pass, the exploration noise and the
+    plan run inside the rollout kernel, and slot k of the returned CUDA tensors `[n_slots, N, ...]` holds what the reference pushes at an
+    env's k-th replan gate — tokens (`task_feats` .. `edge_valid`, `context`), `logits`, `scores`, `noise` (times edge_valid), `selected`,
+    `s_wps_before` / `s_wps_after`, the `next_*` tokens and `done`.  Added: `valid` [n_slots, N] (the slot holds a transition) and
+    `step_reward` = (s_wps_after - s_wps_before) / 20.  `n_gates` [N] counts every gate that fired: where it exceeds `n_slots` (default
+    min(n_steps, 64)) the later gates were planned without noise and not recorded.  `noise_std`: the draws are
+    `torch.randn(..., generator=generator) * noise_std` in float32 on the device (None: no exploration, the scores of `pair_scores`).
+    `rings`: reuse the tensors of a previous call.  Nothing crosses PCIe except the 8-byte seeds."""
+    import torch
+
+    dev = torch.device("cuda", env.device_index if device is None else device)
+    G = min(int(n_steps), 64) if n_slots is None else int(n_slots)
+    shapes = env.rl_record_shapes(G)
+    tdt = {np.float32: torch.float32, np.uint8: torch.uint8, np.int32: torch.int32, np.float64: torch.float64}
+    if rings is None:
+        rings = {name: torch.empty(shape, dtype=tdt[dtype], device=dev) for name, (shape, dtype) in shapes.items()}
+    else:
+        rings = {name: rings[name] for name in shapes}
+    noise = None
+    if noise_std is not None:
+        noise = torch.randn(shapes["scores"][0], generator=generator, dtype=torch.float32, device=dev) * float(noise_std)
+    # as in il_record: what torch's current stream still has queued on these blocks (the draws above included) comes first ...
+    env.wait_stream(torch.cuda.current_stream(dev).cuda_stream)
+    env.rollout_rl_record(np.asarray(seeds, dtype=np.uint64), n_steps, interval, True, rings, noise=noise)
+    env.sync()  # ... and the rings are complete before torch's stream touches them
+    out = dict(rings)
+    if noise is not None:
+        out["noise"] = noise
+    out["valid"] = torch.arange(G, device=dev)[:, None] < rings["n_gates"].clamp(max=G)[None, :]
+    diff = rings["s_wps_after"] - rings["s_wps_before"]
+    out["step_reward"] = torch.div(diff, torch.full_like(diff, 20.0))  # tensor / tensor: IEEE division (see il_record)
+    return out
+
+
 def rl_stream(env: BatchedMultiUAVEnv, seeds, policy, n_steps: int = 150, interval: int = 20, kind: str = "pair", max_tasks: int = 32,
               max_agents: int = 16, gate: str = "trainer", device=None, fused: bool = True, run_ahead: bool = False, max_steps: int = 0, **plan_kw):
     """run_rl_episode (experiments/train_pair_cost.py:132-156) for every env of the batch at once, the policy in the loop:
@@ -158,7 +195,8 @@ def rl_run_stream(env: BatchedMultiUAVEnv, seeds, policy, interval: int = 20, ki
     `replanned` == 1; `next_tok` rows of the others are stale) and then steps each env with empty actions up to ITS next gate (at most
     `max_steps` steps per launch when > 0: an env cut short is not at a gate, `replanned` 0 at the next launch, and simply continues).
     Envs advance by different numbers of steps per launch (`n_stepped`); the stream ends when every episode has ended.  Also yielded:
-    `park` (u8: bit 0 terminated, bit 1 truncated, bit 2 at a gate) and `reward_sum` (env rewards over the launch's steps).  All tensors
+    `park` (u8: bit 0 terminated, bit 1 truncated, bit 2 at a gate), `reward_sum` (env rewards over the launch's steps) and `s_wps` (f64 [2, N]:
+    S_WPS before / after the planned step, what `step_reward` is made of).  All tensors
     are reused between yields (two alternating token buffer sets, as in `rl_stream`)."""
     import torch
 
@@ -190,7 +228,7 @@ def rl_run_stream(env: BatchedMultiUAVEnv, seeds, policy, interval: int = 20, ki
                    next_tok=nxt, s_wps=s_wps, done=done, park_tok=prk, n_stepped=n_stepped, park=park, reward_sum=reward_sum, max_steps=max_steps, **plan_kw)
         env.sync()
         yield k, {"tok": tok, "scores": scores, "selected": selected, "replanned": replanned, "step_reward": torch.div(s_wps[1] - s_wps[0], twenty),
-                  "next_tok": nxt, "done": done, "n_stepped": n_stepped, "park": park, "reward_sum": reward_sum, "park_tok": prk}
+                  "next_tok": nxt, "done": done, "n_stepped": n_stepped, "park": park, "reward_sum": reward_sum, "park_tok": prk, "s_wps": s_wps}
         k += 1
         if bool(((park & 3) != 0).all()):
             return

@@ -115,6 +115,16 @@ class MuavtaDims(C.Structure):
     ]
 
 
+RL_TOK_RINGS = ("task_feats", "task_mask", "agent_feats", "agent_mask", "edge_valid")   # build_tokens(env) at the gate; "next_" + name: after the step
+RL_RINGS = RL_TOK_RINGS + ("context", "logits", "scores", "noise", "selected", "s_wps_before", "s_wps_after") + tuple(
+    "next_" + n for n in RL_TOK_RINGS + ("context",)) + ("done", "step", "n_gates")
+
+
+class MuavtaRlRings(C.Structure):
+    """include/muavta.h: MuavtaRlRings (device pointers of the per-gate transition rings of muavta_rollout_record in MUAVTA_ALLOC_MLP_PAIR mode)."""
+    _fields_ = [("n_slots", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_void_p) for n in RL_RINGS]
+
+
 class MuavtaRecord(C.Structure):
     """include/muavta.h: MuavtaRecord (device pointers of the per-step rings of muavta_rollout_record)."""
     _fields_ = [("kind", C.c_int32), ("max_tasks", C.c_int32), ("max_agents", C.c_int32), ("reserved", C.c_int32),
@@ -122,7 +132,8 @@ class MuavtaRecord(C.Structure):
                 ("agent_mask", C.c_void_p), ("agent_ids", C.c_void_p), ("edge_valid", C.c_void_p), ("n_urgent", C.c_void_p),
                 ("expert_mask", C.c_void_p), ("replanned", C.c_void_p), ("s_wps", C.c_void_p),
                 ("obs_tasks", C.c_void_p), ("obs_legal", C.c_void_p), ("obs_pad", C.c_void_p), ("obs_agents", C.c_void_p),
-                ("obs_flags", C.c_void_p), ("obs_reward", C.c_void_p), ("obs_done", C.c_void_p)]
+                ("obs_flags", C.c_void_p), ("obs_reward", C.c_void_p), ("obs_done", C.c_void_p),
+                ("rl", C.POINTER(MuavtaRlRings))]
 
 
 class _Cfg:

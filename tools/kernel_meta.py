@@ -16,7 +16,8 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # committed tables use: REC = the recording rollout, BL = AllocBaseline, PM = AllocLearned<POL>, and with it (or for k_pair_scores alone)
 # CX = PolContextPair, CO = PolCoalition, W = the variant over the wide 48 x 64 token pads (PolPairWide, PolContextPairWide), UW =
 # AllocUrgencyWide (Urgency-Pair at those pads).  AllocHungarian and PolPair print nothing.
-TAGS = (("REC", "Lb1E"), ("BL", "AllocBaseline"), ("UW", "AllocUrgencyWide"), ("PM", "AllocLearned"), ("CX", "PolContextPair"), ("CO", "PolCoalition"), ("W", "PairWide"))
+TAGS = (("REC", "Lb1E"), ("BL", "AllocBaseline"), ("UW", "AllocUrgencyWide"), ("PM", "AllocLearned"), ("RL", "AllocLearnedRl"), ("CX", "PolContextPair"), ("CO", "PolCoalition"),
+        ("W", "PairWide"))  # RL = AllocLearnedRl<POL>: the rollout that records the RL transitions (printed behind PM)
 
 
 def short(name):
