@@ -39,7 +39,12 @@ and are compared with the oracle:
   lanes     ONE handle with two state lanes (muavta_set_lanes): seeded rollouts queued back to back, every batch read through
             muavta_rollout_metrics_back while the next one runs; all 30 metrics of every batch.
 
-    python tests/fuzz_device.py [first_k [n_configs [seeds_per_config]]] [--more]
+  learned   (--learned; not one of LEGS) a handle in a learned allocator mode — 'mlp_pair', 'mlp_context_pair', 'mlp_coalition', kind and weight
+            set rotating with the config number — beside one oracle per env through tests/learned_lockstep.py::device_lockstep: tokens,
+            context, logits against the host twin, the staged plan against the oracle's scored planner fed the device's scores, every field
+            and the observation after every step, final metrics and n_replans.
+
+    python tests/fuzz_device.py [first_k [n_configs [seeds_per_config]]] [--more] [--learned]
 
 Lives under tests/ because it uses the oracle as its checker."""
 import os
@@ -810,6 +815,34 @@ def lanes(k, w, log):
     return "ok"
 
 
+def learned(k, w, log):
+    import learned_lockstep as LL
+
+    cfg, interval, seed = w["cfg"], w["interval"], w["seed"]
+    kind = ("pair", "context", "coalition")[k % 3]
+    wname = LL.WEIGHT_SETS[kind][(k // 3) % 3]
+    tile = tiles_for(cfg)[(k // 9) % len(tiles_for(cfg))]
+    pads = LL.WIDE if kind != "coalition" and tile[0] >= 24 and (k // 2) % 2 else None
+    p = params(cfg, tile)
+    n = 2
+    seeds = np.array([seed - i if seed > 2 ** 62 else seed + i for i in range(n)], dtype=np.uint64)
+    wts = LL.weights(kind, wname)
+    env = LL.make_env(p, n, kind, wts, pads, tile)
+    tag = f"k={k} learned {kind} {wname} tile {tile} pads {pads or LL.TABLE[kind].pads()} interval {interval}"
+    try:
+        res = LL.device_lockstep(env, [orc.OracleEnv(p) for _ in range(n)], seeds, kind, wts, interval, k % 2 == 0, pads, tag=tag)
+        if res["flagged"]:
+            return "overflow"
+        for i, f in enumerate(res["final"]):
+            assert np.array_equal(f["metrics"], f["oracle"].metrics()) and int(f["scalars"][23]) == f["oracle"].dims()["n_replans"], f"{tag} seed {seeds[i]}: final metrics / n_replans"
+    except AssertionError as exc:
+        log(f"LEARNED MISMATCH {str(exc)[:600]}")
+        return "bad"
+    finally:
+        env.close()
+    return "ok"
+
+
 LEGS = ("stepwise", "scored", "lists", "rl", "rings", "mutators", "resume", "ilrings", "inflight", "rlrun", "steprun", "lanes")
 
 
@@ -844,6 +877,9 @@ if __name__ == "__main__":
                 tot["rlrun_" + rlrun(k, w, log)] += 1
                 tot["steprun_" + steprun(k, w, log)] += 1
                 tot["lanes_" + lanes(k, w, log)] += 1
+            if "--learned" in sys.argv:
+                r = "learned_" + learned(k, w, log)
+                tot[r] = tot.get(r, 0) + 1
         except Exception as exc:  # a configuration the library rejects (muavta_create's argument checks): reported, not fatal
             if "overflowed a tile" in str(exc):  # (a capacity flag met by a call that refuses flagged batches, e.g. the facade's metrics)
                 tot["capacity_exceptions"] = tot.get("capacity_exceptions", 0) + 1
@@ -852,4 +888,6 @@ if __name__ == "__main__":
             log(f"k={k} ERROR {type(exc).__name__}: {str(exc)[:300]}")
         if (k - first) % 10 == 9:
             log(f"... {k - first + 1} configs, {time.time() - t0:.0f} s: {tot}")
+    if "--learned" in sys.argv:
+        log(f"learned: {({key: v for key, v in tot.items() if key.startswith('learned_')})}")
     log(f"configs {first}..{first + n_cfg - 1}, {n_seeds} seeds each on 3 tiles: {tot}  escalated envs compared: {ESCALATED[0]}  ({time.time() - t0:.0f} s)")
