@@ -56,8 +56,9 @@ struct DevParams {
   int32_t rw_plain;               // every reward weight is finite and >= 0 and reward_norm_factor > 0: a step whose reward terms are all +0.0 has reward +0.0
 };
 
-template <int A_, int T_, int H_, int R_, int E_, int Q_, bool REGC_ = false, bool OTFC_ = false, bool SLIM_ = false, bool TIMES_LDS_ = false>
+template <int A_, int T_, int H_, int R_, int E_, int Q_, bool REGC_ = false, bool OTFC_ = false, bool SLIM_ = false, bool TIMES_LDS_ = false, bool SCAN_ONCE_ = false>
 struct Tile {
+  static constexpr bool SCAN_ONCE = SCAN_ONCE_;  // step() walks t_order ONCE (Sim::slot_pass, sim/world.inc) for sensing, the pre-checks and the end-of-step fast path
   static constexpr bool TIMES_LDS = TIMES_LDS_;  // initTime / doneTime of the tasks live in LDS instead of the HBM record (TaskTimes below): the tiles with room for 16 x T more bytes
   static constexpr bool SLIM = SLIM_;  // next_free_* / orgReqs / doneReqs / mission areas live in the HBM record instead of LDS (the 24-agent tile: 16 envs per CU need <= 10 KiB)
   static constexpr bool REGC = REGC_;  // the allocator builds the LSAP cost columns in registers (while they fit one per lane): no A x T cost tile in LDS
@@ -208,12 +209,19 @@ struct alignas(16) EnvState : QueueSide<TL::A, TL::T, !TL::SLIM>, TaskTimes<TL::
 #ifndef MUAVTA_TIMES_LDS
 #define MUAVTA_TIMES_LDS 1
 #endif
-typedef Tile<16, 40, 16, 48, 40, 10, true, false, false, MUAVTA_TIMES_LDS != 0> Tile16;
+// MUAVTA_SCAN_ONCE (1): one pass over the live task slots per step instead of three (Tile::SCAN_ONCE).  One bit per tile: 1 the 16-agent
+// tile, 2 the 24-agent tile, 4 the 64-agent tile; 0 is the step as it was, the same machine code in every function.  The 16-agent
+// tile ships with it (+2.7 % on the headline, profiles/r08_slot_scan_ab.json).  The larger tiles gained 0.7 % / 1.5 % with 7 and no
+// spill, but stay off until a 64 x 128 case with more than 64 live slots (two trips of the pass) is tested against the oracle.
+#ifndef MUAVTA_SCAN_ONCE
+#define MUAVTA_SCAN_ONCE 1
+#endif
+typedef Tile<16, 40, 16, 48, 40, 10, true, false, false, MUAVTA_TIMES_LDS != 0, (MUAVTA_SCAN_ONCE & 1) != 0> Tile16;
 #ifndef MUAVTA_TILE24_SLIM  // experiment knob (0: QueueSide in LDS like the other tiles: 11.6 KB per env, 14 envs per CU)
 #define MUAVTA_TILE24_SLIM 1
 #endif
-typedef Tile<24, 48, 24, 88, 32, 12, true, false, MUAVTA_TILE24_SLIM != 0> Tile24;  // escort 24-UAV config: queue <= 10, pending <= 60, events <= 20 measured
-typedef Tile<64, 128, 48, 128, 96, 12, true, true> Tile64;  // register cost columns up to 64 LSAP columns, on-the-fly LDS solver beyond
+typedef Tile<24, 48, 24, 88, 32, 12, true, false, MUAVTA_TILE24_SLIM != 0, false, (MUAVTA_SCAN_ONCE & 2) != 0> Tile24;  // escort 24-UAV config: queue <= 10, pending <= 60, events <= 20 measured
+typedef Tile<64, 128, 48, 128, 96, 12, true, true, false, false, (MUAVTA_SCAN_ONCE & 4) != 0> Tile64;  // register cost columns up to 64 LSAP columns, on-the-fly LDS solver beyond
 
 #define MUAVTA_REL_ROW 29  // doubles per release-log row (include/muavta.h: MUAVTA_F_RELEASE_LOG)
 #define MUAVTA_RNG_STREAMS 4

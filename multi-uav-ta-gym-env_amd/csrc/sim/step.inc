@@ -171,6 +171,7 @@
       if (lane == 0) step_serial_b2();
     }
     lds_sync();
+    if constexpr (TL::SCAN_ONCE) { step_tail_one_pass(r_action, r_distance, r_quality, r_squality); return; }
     if (!ABL(6)) {
     if (P.escort_enabled) sync_escorts_coop();
     PROF(6);
@@ -213,6 +214,40 @@
     lds_sync();
     PROF(8);
     if (!ABL(8)) finish_step_parallel(true);
+    PROF(9);
+  }
+  // The rest of step() behind the threat update where the tile walks its live slots once (TL::SCAN_ONCE): escort sync, sensing, reveals
+  // and windows, the reward / done bookkeeping and the end-of-step GC, in the order above.  The pass sits behind the last phase that
+  // can create, retire or move a task before sensing (step_serial_b2, or the escort sync where escorts are enabled).
+  // What its results rest on: between the pass and finish_step_parallel only process_lists_coop touches a task, a pending reveal
+  // or an agent's queue.  A due reveal sets TF_KNOWN_ALL and `known` bits, adds to a_gone and packs the pending list — nothing
+  // behind sensing reads any of them in this step.  A window expiry sets status 2 and TF_REACHED and empties the queues of the
+  // agents heading the task: `blocking`, `ret`, the agents' idle / responding flags change, so the pass is taken again behind it
+  // (as the second scan_slots() and the walk of finish_step_parallel did).  t_order / open_slot / n_order / n_open are written
+  // by neither, nor by sensing or step_serial_c.
+  DEV void step_tail_one_pass(double r_action, double r_distance, double r_quality, double r_squality) {
+    SlotScan sc;
+    if (!ABL(6) && P.escort_enabled) sync_escorts_coop();
+    PROF(6);
+    slot_pass(sc, true, !ABL(6));
+    if (!ABL(6)) sense_parallel(sc.nc);  // _wps_update_sensing (:1506-1523): before the reveals
+    lds_sync();
+    PROF(7);
+    if (!ABL(7))
+    {
+      const bool any_due = !ABL(12) && sc.any_due;
+      const bool any_exp = !ABL(12) && P.hard_windows && sc.any_expiring;
+      PROF(28);
+      if (any_due || any_exp) process_lists_coop(any_due, any_exp);
+      lds_sync();
+      PROF(29);
+      if (any_exp) slot_pass(sc, false, false);
+      PROF(32);
+      if (!ABL(11) && lane == 0) step_serial_c(r_action, r_distance, r_quality, r_squality, sc.n_idle, sc.responding, !sc.any_blocking);
+    }
+    lds_sync();
+    PROF(8);
+    if (!ABL(8)) finish_step_parallel(true, &sc);
     PROF(9);
   }
 

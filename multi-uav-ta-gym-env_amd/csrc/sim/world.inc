@@ -431,15 +431,79 @@
     }
   }
 
+  // The ONE pass over the live task slots of a step (TL::SCAN_ONCE).  step() used to walk S.t_order three times — the sensing candidates
+  // (sense_parallel), the pre-checks `expiring` / `blocking` with the pending-reveal test beside them (scan_slots), and the fast-path test
+  // of finish_step_parallel — each its own chain "t_order[k] -> that slot's fields -> ballot".  Nothing between the three creates,
+  // retires, moves or re-flags a task, except a window expiry in process_lists_coop (see step()), so one walk answers all of them.
+  // Two LDS round trips: (1) the list lengths, the lane's t_order / open_slot entry, its pending reveal's time and its agent's state and
+  // queue length; (2) the five fields of its slot.  Every index is clamped into its array instead of guarded, so that the loads of a
+  // trip do not wait for the lengths; what a lane beyond a list read is masked out of the predicates.
+  // Only wave-uniform values leave the pass (SGPRs): nothing per lane stays live across process_lists_coop / step_serial_c.
+  struct SlotScan {
+    int nc = 0;                 // sensing candidates compacted into X.roundT, in list order (first pass only)
+    int n_idle = 0;             // live agents with an empty queue
+    bool any_due = false;       // a pending reveal is due (first pass only)
+    bool any_expiring = false;  // a hard window ran out on a task that is not retired
+    bool any_blocking = false;  // a live task still counts against mission completion
+    bool responding = false;    // a live agent has a queue
+    bool any_ret = false;       // a listed slot is retired: finish_step_parallel has slots to collect
+    bool any_diff = false;      // t_order and open_slot (last_tasks_info) are not the same list
+  };
+  // first: with the sensing candidates and the pending-reveal test; the pass after an expiry needs neither (sensing comes before
+  // reveals and windows, and the reveals of this step are done)
+  DEV void slot_pass(SlotScan& sc, bool first, bool sense) {
+    const int nO = S.n_order, no = S.n_open, np = S.n_pending;
+    const int ai = lane < A ? lane : A - 1;
+    const int ast = S.a_state[ai], aql = S.a_qlen[ai];
+    bool due = false;
+    if (first) {
+      if constexpr (R <= WG) { due = lane < np && tnow >= S.pend_time[lane < R ? lane : R - 1]; }
+      else for (int k = lane; k < np; k += WG) due |= tnow >= S.pend_time[k];
+    }
+    const bool want_cand = first && sense && P.sense_radius > 0;
+    int16_t* cand = X.roundT;  // T entries
+    int nc = 0;
+    bool expiring = false, blocking = false, ret = false, diff = false;
+#pragma unroll
+    for (int base = 0; base < T; base += WG) {
+      if (base > 0 && base >= nO) break;  // (uniform)
+      const int k = base + lane, ki = k < T ? k : T - 1;
+      const bool in = k < nO;
+      const int s_ = S.t_order[ki], os = S.open_slot[ki];
+      const int s = s_ < T ? s_ : T - 1;  // (an entry beyond the list is whatever the row last held)
+      const int fl = S.t_flags[s], st = S.t_status[s], dl = S.t_deadline[s], ty = S.t_type[s], cr = S.t_created[s];
+      expiring |= in && (fl & TF_DEADLINE) && st != 2 && tnow > dl;
+      blocking |= in && !((fl & TF_ESCORT) || ty == MUAVTA_DET || ty == MUAVTA_HOLD || st == 2);  // !counts_for_mission_done(s)
+      ret |= in && st == 2;
+      diff |= in && (k >= no || os != s);
+      if (want_cand) {  // (uniform) sense_parallel's predicate and compaction
+        const bool c = in && st != 2 && !(fl & TF_KNOWN_ALL) && (cr > 0 || (fl & TF_DEADLINE));
+        const unsigned long long m = __ballot(c);
+        if (c) cand[nc + prefix_count(m)] = s;
+        nc += __popcll(m);
+      }
+    }
+    const bool live = lane < P.n_agents && ast != -1;
+    if (first) { sc.nc = nc; sc.any_due = __ballot(due) != 0ull; }
+    sc.any_expiring = __ballot(expiring) != 0ull;
+    sc.any_blocking = __ballot(blocking) != 0ull;
+    sc.any_ret = __ballot(ret) != 0ull;
+    sc.any_diff = no != nO || __ballot(diff) != 0ull;
+    sc.n_idle = __popcll(__ballot(live && aql == 0));
+    sc.responding = __ballot(live && aql != 0) != 0ull;
+  }
+
   // _wps_update_sensing (:1506-1523).  First the wave compacts the slots that can be sensed at all (dynamic,
   // open) by ballot; then lane = (agent a, candidate sub-row) with the agent's position in registers.  The
   // test `norm(d) <= sense_radius` is done on the squared form: sqrt is monotone and correctly rounded, so
   // it equals `fma(dy,dy,dx*dx) <= bound` with the bound precomputed on the host (no sqrt per pair).
-  DEV void sense_parallel() {
+  // nc_scan (TL::SCAN_ONCE): slot_pass has compacted the candidates already, that many
+  DEV void sense_parallel(int nc_scan = 0) {
     if (P.sense_radius <= 0) return;
     const int nA = P.n_agents, nO = S.n_order;
     int16_t* cand = X.roundT;  // T entries
     int nc = 0;
+    if constexpr (TL::SCAN_ONCE) nc = nc_scan; else
     for (int base = 0; base < nO; base += WG) {
       const int k = base + lane;
       int s = -1;
@@ -576,7 +640,16 @@
   // ---------------------------------------------------------------- end of step: slot GC + open list
   // Retired slots are recycled unless a LIVE agent still queues them (their type/position is read by
   // the switch penalty and expected-distance terms, :852-861,:1219-1220).  Parallel over slots.
-  DEV void finish_step_parallel(bool gc) {
+  // sc (TL::SCAN_ONCE): step()'s slot pass holds the fast-path test already — on the steps that take it (most: no task created or retired) the
+  // lists are not walked again.  (The other steps walk them below as before: they are about to rewrite both lists anyway.)
+  DEV void finish_step_parallel(bool gc, const SlotScan* sc = nullptr) {
+    if constexpr (TL::SCAN_ONCE) {
+      if (gc && sc && !sc->any_ret && !sc->any_diff) {  // the fast path below
+        if (lane == 0) { S.n_act = 0; S.list_stale = 0; }
+        lds_sync();
+        return;
+      }
+    }
     if (gc) {
       // fast path: no live slot is retired and every live slot is already listed as open (no task was created
       // or retired since the lists were built) -> t_order / last_tasks_info are unchanged
